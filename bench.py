@@ -2,12 +2,17 @@
 """bench.py — images/sec of the ResNet-v1.5-50 training step (forward + backward + fused Nesterov/L2/EMA update
 [+ RCCL gradient all-reduce]) on synthetic 224x224x3 batches, B = 256 per GPU, on N MI355X of one node.
 
-    python bench.py --gpus N --steps K --warmup W [--dtype fp32|bf16|fp16] [--batch 256]
+    python bench.py --gpus N --steps K --warmup W [--dtype fp32|bf16|fp16] [--batch 256] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one synthetic batch already resident in HBM.  Rank 0 prints ONE JSON line.
 Default workload = BASELINE.json configs[1] (fp32, B=256, 1 GPU); `--dtype bf16` runs configs[2]'s arithmetic.
-At N=1 the line also carries:
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, the result line (metric, value, unit,
+ms_per_step = milliseconds per timed step, ...).  Everything else below is measured only with --full.
+--dump-outputs DIR: after the timed steps, what the last timed step returned to its caller (`_step(fetch=False)`: loss, y_true, y_pred) is
+written as DIR/<name>.npy in float32 (an array of more than DUMP_MAX_ELEMS elements as a fixed, seeded sample of its elements).  The
+weights and the batch are seeded, so two builds run with the same arguments can be compared output for output.
+With --full, at N=1, the line also carries:
   roofline     — the dominant kernel's algorithmic FLOP/s (HIP events around every launch of that kernel in an extra,
                  instrumented pass over the same launch lists; torch's current stream IS the launch stream) against the
                  dense MFMA peak of the dtype (MI355X_MICROARCH.md: fp32 157.3 TFLOP/s, bf16 2500 TFLOP/s)
@@ -52,6 +57,9 @@ def parse():
     ap.add_argument('--batch', type=int, default=None, help='per-GPU batch (default 256; 512 for --model efficientnet_b0)')
     ap.add_argument('--model', default='resnet50', choices=['resnet50', 'efficientnet_b0', 'deeplabv3plus'],
                     help='resnet50 = the headline workload (BASELINE configs[1]/[2]); efficientnet_b0 = configs[3], deeplabv3plus = configs[4] on one GPU (secondary, SURVEY 8f-2 / 8f-3)')
+    ap.add_argument('--full', action='store_true', help='also measure everything beside the headline figure: roofline (instrumented pass), fetch_true, the bf16 / fp16 / '
+                    'EfficientNet-B0 / DeepLabv3+ secondaries and the CPU baselines (the --no-* switches below take single parts out again)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step returned (loss, y_true, y_pred) as DIR/<name>.npy (float32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-secondary', action='store_true')
     ap.add_argument('--no-roofline', action='store_true', help='A/B runs: timed steps only (no instrumented pass, no roofline object)')
@@ -61,6 +69,8 @@ def parse():
     ap.add_argument('--all-kernels', action='store_true', help='kernel_ms_per_step lists every C-ABI entry point / kernel, not the top 14')
     ap.add_argument('--layers', action='store_true', help='print a per-launch table (stderr) from the instrumented pass')
     args = ap.parse_args()
+    if (args.layers or args.all_kernels) and not args.full:
+        ap.error('--layers / --all-kernels read the instrumented pass: add --full')
     if args.batch is None:
         args.batch = {'efficientnet_b0': 512, 'deeplabv3plus': 16}.get(args.model, 256)
     return args
@@ -87,10 +97,29 @@ def build_model(args, dtype, world):
 
 
 def run_steps(opt, n, fetch=False):
+    """n steps as the training loop issues them; returns what the last one returned (None for n = 0)"""
+    last = None
     for _ in range(n):
         opt._update_learning_rate()
-        opt._step(None, fetch=fetch)
+        last = opt._step(None, fetch=fetch)
         opt.curr_step += 1
+    return last
+
+
+DUMP_MAX_ELEMS = 4 << 20           # per array: three float32 arrays stay under 48 MB
+
+
+def dump_outputs(path, last):
+    """--dump-outputs: the (loss, y_true, y_pred) device tensors of the last timed step as float32 .npy files.  An array with more than
+    DUMP_MAX_ELEMS elements (DeepLabv3+: 16 x 513 x 513 x 19 per-pixel predictions) is written as the elements at fixed, seeded flat
+    indices (the same for every run of the same shape)."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in zip(('loss', 'y_true', 'y_pred'), last):
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(20240229).integers(0, a.size, DUMP_MAX_ELEMS))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
 
 
 # kernel symbols (prefixes) behind the streaming C-ABI calls whose PMC bytes are summed per call (only calls that own their symbols in the
@@ -179,7 +208,7 @@ def timed(opt, steps, warmup, world, autotune=False):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     with ctx:
-        run_steps(opt, steps)
+        last = run_steps(opt, steps)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -189,7 +218,7 @@ def timed(opt, steps, warmup, world, autotune=False):
         t = torch.tensor([dt], dtype=torch.float64, device='cuda')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    return dt
+    return dt, last
 
 
 # ---- per-kernel timing (instrumented pass) ---------------------------------------------------------------------
@@ -709,7 +738,9 @@ def main():
         init_process_group('cuda:{}'.format(local_device()))
 
     model, opt = build_model(args, args.dtype, world)
-    dt = timed(opt, args.steps, args.warmup, world, args.autotune)
+    dt, last = timed(opt, args.steps, args.warmup, world, args.autotune)
+    if args.dump_outputs and rank == 0:                   # (before any further step of a --full run overwrites the buffers)
+        dump_outputs(args.dump_outputs, last)
     ms = dt / args.steps * 1e3
     ips = args.batch * world * args.steps / dt
     if args.model != 'resnet50':
@@ -721,7 +752,7 @@ def main():
                'config': {'workload': '{} {} {}x{} synthetic training step (BASELINE {}), batch={}/GPU'.format(title[0], args.dtype, title[1], title[1], title[2], args.batch),
                           'global_batch': args.batch * world, 'parallelism': 'dp{}'.format(world), 'ema': not args.no_ema, 'fetch': False},
                'conv_macs_per_image': int(model.conv_macs), 'params': int(model.params)}
-        if world == 1 and not args.no_roofline:
+        if world == 1 and args.full and not args.no_roofline:
             out.update(streaming_roofline(model, args.dtype, args.batch, args.model, layers=args.layers, all_kernels=args.all_kernels))
         if rank == 0:
             print(json.dumps(out))
@@ -741,7 +772,7 @@ def main():
         'e2e_mfma_frac': round(ips / world * executed_flop_per_image(args.dtype) / (PEAK_TFLOPS[args.dtype] * 1e12), 4),
         'direct_equivalent_frac': round(ips / world * TRAIN_FLOP_PER_IMAGE / (PEAK_TFLOPS[args.dtype] * 1e12), 4),
     }
-    if world == 1 and not args.no_roofline:
+    if world == 1 and args.full and not args.no_roofline:
         # the reference's own _step also copies loss, Y_all and pred to the host every step (optimizers.py:590-594: a device sync per step);
         # `value` skips that (config.fetch = false) — this is the same step WITH it, over min(steps, 10) steps
         nf = min(args.steps, 10)
@@ -829,7 +860,7 @@ def main():
             import argparse as _a
             a2 = _a.Namespace(**vars(args))
             m2, o2 = build_model(a2, 'bf16', 1)
-            dt2 = timed(o2, args.steps, args.warmup, 1, args.autotune)
+            dt2, _ = timed(o2, args.steps, args.warmup, 1, args.autotune)
             ips2 = args.batch * args.steps / dt2
             out['bf16'] = {'value': round(ips2, 2), 'unit': 'images/sec', 'ms_per_step': round(dt2 / args.steps * 1e3, 3),
                            'e2e_mfma_frac': round(ips2 * executed_flop_per_image('bf16') / (PEAK_TFLOPS['bf16'] * 1e12), 4)}
@@ -837,7 +868,7 @@ def main():
             torch.cuda.empty_cache()
             # the reference's own half precision: fp16 storage + loss scaling (same kernels, the f16 MFMA instead of the bf16 one)
             m2, o2 = build_model(a2, 'fp16', 1)
-            dt2 = timed(o2, args.steps, args.warmup, 1, args.autotune)
+            dt2, _ = timed(o2, args.steps, args.warmup, 1, args.autotune)
             out['fp16'] = {'value': round(args.batch * args.steps / dt2, 2), 'unit': 'images/sec', 'ms_per_step': round(dt2 / args.steps * 1e3, 3), 'loss_scaling_factor': 128.0}
             del m2, o2
             torch.cuda.empty_cache()
@@ -846,7 +877,7 @@ def main():
                 a3 = _a.Namespace(**vars(args))
                 a3.model, a3.batch = mdl, bsz
                 m3, o3 = build_model(a3, 'bf16', 1)
-                dt3 = timed(o3, args.steps, args.warmup, 1, False)
+                dt3, _ = timed(o3, args.steps, args.warmup, 1, False)
                 out[key] = {'value': round(bsz * args.steps / dt3, 2), 'unit': 'images/sec', 'ms_per_step': round(dt3 / args.steps * 1e3, 3), 'batch': bsz,
                             'config': 'BASELINE configs[3] (EfficientNet-B0, 224x224)' if mdl == 'efficientnet_b0' else 'BASELINE configs[4] on one GPU (DeepLabv3+, 513x513)'}
                 sr = streaming_roofline(m3, 'bf16', bsz, mdl)                # (`bench.py --model ...` prints the full table)

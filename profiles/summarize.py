@@ -77,10 +77,10 @@ def build_id():
 def main(root, rnd='round2'):
     here = os.path.dirname(os.path.abspath(__file__))
     # (tag of the raw directories / output files, --dtype, batch, PMC command)
-    configs = [('fp32', 'fp32', 256, 'python3 bench.py --steps 1 --warmup 1 --dtype fp32 --no-secondary --no-cpu-baseline'),
-               ('bf16', 'bf16', 256, 'python3 bench.py --steps 1 --warmup 1 --dtype bf16 --no-secondary --no-cpu-baseline'),
-               ('efficientnet_b0_bf16', 'bf16', 512, 'python3 bench.py --model efficientnet_b0 --dtype bf16 --steps 1 --warmup 1'),
-               ('deeplabv3plus_bf16', 'bf16', 16, 'python3 bench.py --model deeplabv3plus --dtype bf16 --steps 1 --warmup 1')]
+    configs = [('fp32', 'fp32', 256, 'python3 bench.py --full --steps 1 --warmup 1 --dtype fp32 --no-secondary --no-cpu-baseline'),
+               ('bf16', 'bf16', 256, 'python3 bench.py --full --steps 1 --warmup 1 --dtype bf16 --no-secondary --no-cpu-baseline'),
+               ('efficientnet_b0_bf16', 'bf16', 512, 'python3 bench.py --full --model efficientnet_b0 --dtype bf16 --steps 1 --warmup 1'),
+               ('deeplabv3plus_bf16', 'bf16', 16, 'python3 bench.py --full --model deeplabv3plus --dtype bf16 --steps 1 --warmup 1')]
     for dt, dtype, batch, cmd in configs:
         for src, tag in (('stats_', ''), ('serial_', 'serial_')):
             st = glob.glob(os.path.join(root, src + dt, '**', '*kernel_stats.csv'), recursive=True)

@@ -104,5 +104,58 @@ def flip_aware_step(spec, state, towers, dev_grads, hp=None, batch_total=None, l
     return loss, pred, g, [ties[e] for e in chosen]
 
 
+def flip_aware_pair(spec, state, towers, grads_a, grads_b, hp=None, batch_total=None, lr_mult=1.0, tol=2e-5, tie_tol=4e-6, max_flips=6, noise_floor=1e-6):
+    """Two device evaluations of the SAME step (same weights, same batch; `state` is the oracle state before it and is left untouched) that
+    differ only in the order of their fp32 sums must agree within `tol` on every gradient tensor — except that a ReLU input within rounding of
+    zero may fall on either side in either of them.  As in flip_aware_step the bar stays and the decisions are accounted for: the effect of
+    inverting each of the oracle's near-ties is measured by the oracle, and a greedy search picks the inversions (either direction: a or b may
+    be the one that left the oracle's branch) after which grads_b - grads_a is within `tol` everywhere.  Returns the list of (tower, ReLU
+    ordinal, flat index) decisions used (empty in the common case); fails when no such set of at most `max_flips` exists."""
+    keys = [k for k in grads_a if np.linalg.norm(grads_a[k]) > noise_floor]
+    norm = {n: max(np.linalg.norm(np.asarray(grads_a[n], np.float64)), 1e-30) for n in keys}
+    resid = {n: np.asarray(grads_b[n], np.float64) - np.asarray(grads_a[n], np.float64) for n in keys}
+
+    def worst(r):
+        return max((float(np.linalg.norm(r[n]) / norm[n]), n) for n in keys)
+    if worst(resid)[0] <= tol:
+        return []
+    ntow = len(towers)
+    probe = {'relu_flips': {}, 'tie_tol': tie_tol}
+    ON.train_step(spec, ON.copy_state(state), None, None, hp=hp, lr_mult=lr_mult, batch_total=batch_total, tower_batches=towers, probe=probe)
+    ties = probe.get('near_ties', [])
+    assert ties, 'gradient {1} differs by {0:.2e} between the two evaluations and the oracle has no ReLU near-tie (|z| <= {2:g} rms) to account for it'.format(*worst(resid), tie_tol)
+    assert len(ties) <= 64, 'too many near-ties ({}) for a flip search'.format(len(ties))
+    base, deltas = {}, []
+    for (ti, k, i) in ties:
+        if ti not in base:
+            base[ti] = ON.train_step(spec, ON.copy_state(state), None, None, hp=hp, lr_mult=lr_mult, batch_total=batch_total, tower_batches=[towers[ti]])[2]
+        gf = ON.train_step(spec, ON.copy_state(state), None, None, hp=hp, lr_mult=lr_mult, batch_total=batch_total, tower_batches=[towers[ti]],
+                           probe={'relu_flips': {(0, k): [i]}})[2]
+        deltas.append({n: (gf[n] - base[ti][n]) / ntow for n in keys})
+
+    def score(r):
+        return sum((np.linalg.norm(r[n]) / norm[n]) ** 2 for n in keys)
+    chosen = []
+    for _ in range(max_flips):
+        if worst(resid)[0] <= tol:
+            break
+        cur, best = score(resid), None
+        for e, d in enumerate(deltas):
+            if e in chosen:
+                continue
+            for sign in (1.0, -1.0):
+                sc = score({n: resid[n] - sign * d[n] for n in keys})
+                if best is None or sc < best[0]:
+                    best = (sc, e, sign)
+        if best is None or best[0] >= cur:
+            break
+        chosen.append(best[1])
+        resid = {n: resid[n] - best[2] * deltas[best[1]][n] for n in keys}
+    w = worst(resid)
+    assert w[0] <= tol, ('gradient {} of the two evaluations stays {:.2e} apart with {} of the oracle\'s {} ReLU near-tie decisions inverted'
+                         .format(w[1], w[0], len(chosen), len(ties)))
+    return [ties[e] for e in chosen]
+
+
 def _assign(dst, src):
     dst.params, dst.stats, dst.accum, dst.ema, dst.ema_stats, dst.step = src.params, src.stats, src.accum, src.ema, src.ema_stats, src.step

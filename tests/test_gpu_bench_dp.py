@@ -57,9 +57,9 @@ def test_bench_without_a_launcher_spawns_its_own_ranks():
 @pytest.mark.parametrize('dtype', ['fp32', 'fp16'])
 def test_bench_single_gpu_line_carries_the_roofline_object(dtype):
     """The N=1 contract: one JSON line with metric / value / ms_per_step and a `roofline` object whose bound follows the dominant
-    kernel's arithmetic intensity (short run at B=32; `cpu_baseline` and the secondary workloads are switched off here — the default
-    `python bench.py` adds them)."""
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '5', '--warmup', '1', '--batch', '32', '--dtype', dtype, '--no-secondary', '--no-cpu-baseline']
+    kernel's arithmetic intensity (short run at B=32 with --full, which is what measures the object; `cpu_baseline` and the secondary
+    workloads are switched off here — `python bench.py --full` adds them)."""
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '5', '--warmup', '1', '--batch', '32', '--dtype', dtype, '--no-secondary', '--no-cpu-baseline']
     r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -77,3 +77,30 @@ def test_bench_single_gpu_line_carries_the_roofline_object(dtype):
     assert 0.0 < out['e2e_mfma_frac'] <= out['direct_equivalent_frac'] and out['executed_flop_per_image'] <= out['train_flop_per_image']
     assert (out['executed_flop_per_image'] < out['train_flop_per_image']) == (dtype == 'fp32')
     assert out['config']['fetch'] is False and out['fetch_true']['value'] > 0.0
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline figure only (no instrumented pass, no secondaries, no CPU baseline), and
+    --dump-outputs DIR leaves what the last timed step returned (loss, y_true, y_pred) as float32 .npy files."""
+    import numpy as np
+    out_dir = str(tmp_path / 'dump')
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '8', '--dump-outputs', out_dir]
+    r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out['steps'] == 2 and out['unit'] == 'images/sec' and out['higher_is_better'] is True and out['dtype'] == 'f32'
+    assert abs(out['value'] - 8 / (out['ms_per_step'] * 1e-3)) <= 0.01 * out['value']
+    for key in ('roofline', 'roofline_by_kernel', 'kernel_ms_per_step', 'fetch_true', 'bf16', 'fp16', 'efficientnet_b0_bf16', 'deeplabv3plus_bf16', 'cpu_baseline'):
+        assert key not in out, key
+    got = {f: np.load(os.path.join(out_dir, f)) for f in sorted(os.listdir(out_dir))}
+    assert sorted(got) == ['loss.npy', 'y_pred.npy', 'y_true.npy']
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert got['y_pred.npy'].shape == (8, 1000) and got['y_true.npy'].shape == (8, 1000)
+    np.testing.assert_allclose(got['y_pred.npy'].sum(-1), 1.0, rtol=1e-4)                # softmax rows
+    np.testing.assert_array_equal(got['y_true.npy'].sum(-1), 1.0)                        # one-hot rows
+    assert got['loss.npy'].size >= 1 and got['loss.npy'].reshape(-1)[0] > 0.0
+    # --layers / --all-kernels read the instrumented pass: refused without --full, before any GPU work
+    r = subprocess.run(cmd + ['--layers'], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 2 and '--full' in r.stderr

@@ -14,7 +14,7 @@ import os     # noqa: E402
 import sys    # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from flip_util import assert_flip_budget, flip_aware_step  # noqa: E402
+from flip_util import assert_flip_budget, flip_aware_pair, flip_aware_step  # noqa: E402
 from oracle import net as ON  # noqa: E402
 from oracle import ops as O   # noqa: E402
 
@@ -295,7 +295,11 @@ def test_resnet_autotuned_tiles_step_matches_oracle():
     """ConvNet.autotune() (bench.py --autotune) pins a tile per conv launch — including the dgrads that carry the masked fan-in and the
     unit-output BN's backward sums (mcn_conv2d_dgrad_addmasked_bnred), whose partial-row count follows the tile.  The step behind the pinned
     tiles is the step of the library's own choice up to the order of fp32 sums (every gradient tensor, 2e-5), and the oracle's in loss and
-    predictions (the per-tensor oracle bar of the untuned step: test_resnet_two_steps_fp32 / ..._bn_statistics_from_conv_epilogue)."""
+    predictions (the per-tensor oracle bar of the untuned step: test_resnet_two_steps_fp32 / ..._bn_statistics_from_conv_epilogue).
+    Which tiles autotune() pins depends on the timings of the run, and a different order of the BN-statistics sums can put a ReLU input that
+    is zero to rounding on the other side (seen on a clean build: 128 x 64 on block_2/res_0/conv_0 moves one decision of block_3/res_2's
+    output and with it every gradient below by up to 9e-3).  The 2e-5 bar stays; such decisions are accounted for as in flip_util — each
+    one a near-tie of the oracle, its effect measured by the oracle, their number within FLIP_BUDGET."""
     import myconvnet_amd as M
     x = np.random.default_rng(63).random((BATCH, 64, 64, 3)).astype(np.float32)
     res = {}
@@ -326,8 +330,9 @@ def test_resnet_autotuned_tiles_step_matches_oracle():
             assert abs(loss - rloss) <= 1e-4 * abs(rloss)
             assert rel_l2(y_pred, rpred) <= 1e-4
     assert abs(res[True][0] - res[False][0]) <= 1e-6 * abs(res[False][0])
-    worst = max((rel_l2(res[True][2][k], v), k) for k, v in res[False][2].items() if np.linalg.norm(v) > 1e-6)
-    assert worst[0] <= 2e-5, worst
+    state = ON.TrainState({k: v.astype(np.float64) for k, v in params.items()}, {k: v.astype(np.float64) for k, v in stats.items()})
+    flips = flip_aware_pair(spec, state, [(x.astype(np.float64), LABELS.astype(np.float64))], res[False][2], res[True][2], batch_total=BATCH, tol=2e-5)
+    assert_flip_budget(flips, 'autotuned step against the step of the library\'s own tiles')
 
 
 def test_resnet_fp32_bn_statistics_from_conv_epilogue():

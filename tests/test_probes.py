@@ -27,14 +27,14 @@ def test_every_probe_patch_still_applies():
     assert not bad, bad
 
 
-def test_every_probe_harness_still_compiles():
+def test_every_probe_harness_still_compiles(tmp_path):
     if not os.path.exists(HIPCC):
         pytest.skip('no hipcc here')
     srcs = sorted(glob.glob(os.path.join(PROBES, '*.hip')))
     assert srcs
 
     def build(src):
-        out = os.path.join('/tmp', 'mcn_probe_' + os.path.basename(src) + '.o')
+        out = str(tmp_path / (os.path.basename(src) + '.o'))         # (pytest's own directory: nothing left beside the sources, nothing shared between users)
         r = subprocess.run([HIPCC, '--offload-arch=gfx950', '-O1', '-std=c++17', '-I' + os.path.join(ROOT, 'myconvnet_amd', 'csrc'), '-c', src, '-o', out],
                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
         return os.path.basename(src), r.returncode, r.stdout[-800:]
