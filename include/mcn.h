@@ -364,6 +364,36 @@ int mcn_channel_scale_bwd(const void* dy, const void* x, const void* m, void* dx
 int mcn_channel_affine(const void* x, const float* scale, const float* shift, void* y, int64_t M, int32_t C,
                        mcn_dtype dtype, void* stream);
 
+/* ---- group normalisation ----------------------------------------------------------------
+ * replaces ConvNet.group_norm (reference convnet.py:1928-2013; called by models/resnet_v1_5_wsgn.py and models/efficientnet_wsgn.py, and
+ * by normalization(norm_type='group'), convnet.py:1765-1769).  x, y: [N][HW][C] NHWC in `dtype`; group g owns channels
+ * [g*C/G, (g+1)*C/G); mean and BIASED variance over HW x C/G in fp32 (tf.nn.moments, convnet.py:2007), per (image, group):
+ *   y = act((x - mean) / sqrt(var + eps) * gamma + beta [+ skip]), rounded once (convnet.py:2008-2012).  HW = 1 is the reference's 2-D [B, C] case.
+ * gamma / beta: fp32 [C]; NULL = 1 / 0 (scale=False / shift=False, convnet.py:1977, 1996).  `skip` (same shape as y, may be NULL) and
+ * `act` (MCN_ACT_NONE or MCN_ACT_RELU; anything else: MCN_E_UNSUPPORTED) are fused as in mcn_bn_fwd_train, with its rounding points.
+ * save_mean / save_invstd: fp32 [N][G], kept for the backward pass; may be NULL (inference: the same kernel with the EMA shadows of
+ * gamma / beta, convnet.py:1999-2000).  C % G != 0: MCN_E_BADARG; C not a multiple of the 16-byte chunk (4 fp32 / 8 two-byte elements):
+ * MCN_E_UNSUPPORTED (the reference's G = 32 never produces it).
+ * path: 0 = library choice; MCN_GN_TWO_PASS = statistics pass + apply pass (any shape); MCN_GN_RESIDENT = one workgroup keeps an image's
+ * slab of a few groups in LDS and reads x once (mcn_gn_resident_ok() != 0; a forced RESIDENT that does not fit: MCN_E_UNSUPPORTED).
+ * Deterministic (no atomics): a repeated call is bit-identical.  workspace: mcn_gn_workspace_bytes(N, HW, C, G), either path.
+ *
+ * mcn_gn_bwd: gradient of the above (tf.gradients through convnet.py:2004-2012 [+ ReluGrad + the add's fan-out]).  Per (n, g), with
+ * m = HW*C/G, xhat = (x - mean)*invstd and dz = dy masked by [y > 0] when act == RELU (y = the stored forward output, required then):
+ *   dx = invstd * (dz*gamma - (1/m) sum_g dz*gamma - xhat * (1/m) sum_g dz*gamma*xhat)
+ *   dgamma[c] = grad_scale * sum_{n,hw} dz*xhat,  dbeta[c] = grad_scale * sum_{n,hw} dz   (either may be NULL: frozen blocks_to_train)
+ *   dskip (may be NULL) receives dz. */
+#define MCN_GN_TWO_PASS 1
+#define MCN_GN_RESIDENT 2
+size_t mcn_gn_workspace_bytes(int32_t N, int64_t HW, int32_t C, int32_t G);
+int32_t mcn_gn_resident_ok(int32_t backward, int32_t N, int64_t HW, int32_t C, int32_t G, mcn_dtype dtype);
+int mcn_gn_fwd(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* save_mean, float* save_invstd,
+               int32_t N, int64_t HW, int32_t C, int32_t G, float eps, mcn_act act, mcn_dtype dtype, int32_t path, void* workspace,
+               size_t workspace_bytes, void* stream);
+int mcn_gn_bwd(const void* dy, const void* x, const void* y, const float* gamma, const float* save_mean, const float* save_invstd,
+               void* dx, void* dskip, float* dgamma, float* dbeta, float grad_scale, int32_t N, int64_t HW, int32_t C, int32_t G,
+               mcn_act act, mcn_dtype dtype, int32_t path, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- element-wise -----------------------------------------------------------------------
  * tf.nn.relu / ReluGrad (convnet.py:2537); x + skip followed by relu (convnet.py:2511, 2537). */
 int mcn_relu_fwd(const void* x, void* y, int64_t n, mcn_dtype dtype, void* stream);

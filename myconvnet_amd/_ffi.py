@@ -22,6 +22,7 @@ ACT_NONE, ACT_RELU, ACT_SWISH, ACT_SIGMOID, ACT_RELU6, ACT_LRELU, ACT_TANH = 0, 
 DECAY_L2, DECAY_L1, DECAY_HUBER = 0, 1, 2
 CONV_FWD, CONV_DGRAD, CONV_WGRAD = 0, 1, 2
 OK, E_BADARG, E_UNSUPPORTED, E_LAUNCH, E_WORKSPACE = 0, -1, -2, -3, -4
+GN_TWO_PASS, GN_RESIDENT = 1, 2
 
 
 class McnError(RuntimeError):
@@ -141,6 +142,10 @@ SIGNATURES = {
     'mcn_ema_update': (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),
     'mcn_bn_running_chain': (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_float, c_void_p]),
     'mcn_bn_running_chain_strided': (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int64, c_float, c_void_p]),
+    'mcn_gn_workspace_bytes': (c_size_t, [c_int32, c_int64, c_int32, c_int32]),
+    'mcn_gn_resident_ok': (c_int32, [c_int32, c_int32, c_int64, c_int32, c_int32, c_int]),
+    'mcn_gn_fwd': (c_int, [c_void_p] * 7 + [c_int32, c_int64, c_int32, c_int32, c_float, c_int, c_int, c_int32, c_void_p, c_size_t, c_void_p]),
+    'mcn_gn_bwd': (c_int, [c_void_p] * 10 + [c_float, c_int32, c_int64, c_int32, c_int32, c_int, c_int, c_int32, c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -36,6 +36,8 @@ if os.environ.get('MCN_EXTRA_CFLAGS'):                   # experiment builds (e.
     import hashlib as _h
     FLAGS += os.environ['MCN_EXTRA_CFLAGS'].split()
     OBJ = os.path.join(CSRC, '_obj_x' + _h.sha1(os.environ['MCN_EXTRA_CFLAGS'].encode()).hexdigest()[:8])
+# per-source flags.  gn.hip: scalar fp32 math only (no v_pk_*_f32 forms; its kernels are HBM-bound, the packed forms buy nothing there)
+SOURCE_FLAGS = {'gn.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
 PROBES = os.environ.get('MCN_KERNEL_PROBES') == '1'
 if PROBES:
     FLAGS.append('-DMCN_KERNEL_PROBES=1')
@@ -70,7 +72,7 @@ def build(force=False, verbose=True):
         obj = os.path.join(OBJ, s.replace('.hip', '.o'))
         objs.append(obj)
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), hdr_time):
-            jobs.append([HIPCC] + FLAGS + ['-c', src, '-o', obj])
+            jobs.append([HIPCC] + FLAGS + SOURCE_FLAGS.get(s, []) + ['-c', src, '-o', obj])
 
     def run(cmd):
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

@@ -7,7 +7,8 @@ reference's ConvNet needs only its `tf.*` calls swapped for the methods here (IN
 What differs by design: there is no TF session — `_build_model` records a static graph once, and
 `compile()` turns it into flat lists of HIP launches (graph.py / executor.py).
 
-Not built (raise NotImplementedError): depthwise conv, weight standardisation, group norms,
+Not built (raise NotImplementedError): depthwise conv, weight standardisation, the normalization()
+dispatcher for anything but 'batch' (group_norm itself is built: a model calls it from _build_model),
 augmentation, dropout rate > 0, transposed conv / upsampling (SURVEY.md §8f "next" rows).
 """
 import math
@@ -408,6 +409,9 @@ class ConvNet(object):
                 mu, sg = a['mu'], a['sigma']
                 a['saved'] = dict(mean=torch.zeros(c, dtype=torch.float32, device=dev), invstd=torch.zeros(c, dtype=torch.float32, device=dev),
                                   bmean=self.batch_stats[mu.offset:mu.offset + c], bvar=self.batch_stats[sg.offset:sg.offset + c])
+            elif n.op == 'gn':
+                ng = n.inputs[0].shape[0] * n.attrs['groups']
+                n.attrs['saved'] = dict(mean=torch.zeros(ng, dtype=torch.float32, device=dev), invstd=torch.zeros(ng, dtype=torch.float32, device=dev))
             elif n.op == 'mulmask':
                 pass                                       # one flat buffer for all masks, below
             elif n.op == 'loss':
@@ -660,7 +664,9 @@ class ConvNet(object):
 
     def normalization(self, x, norm_type='batch', norm_param=None, scale=True, shift=True, zero_scale_init=False, epsilon=1e-3,
                       scope='norm'):
-        """reference convnet.py:1757-1778."""
+        """reference convnet.py:1757-1778.  Only 'batch' is dispatched: norm_type='group' still raises although group_norm() is built
+        (tests/test_host_logic.py pins the NotImplementedError; routing it to self.group_norm(x, num_groups=norm_param, ...) as
+        convnet.py:1765-1769 does is the follow-up) — a model reaches group norm by calling self.group_norm directly."""
         if norm_type is None:
             return x
         if norm_type.lower() == 'batch':
@@ -697,6 +703,34 @@ class ConvNet(object):
         y = self.graph.tensor(x.shape, x.dtype, name, self._channel_first)
         self.graph.node('bn', [x], [y], scope=name, gamma=gamma, beta=beta, mu=mu, sigma=sigma, eps=epsilon,
                         momentum=self._batch_norm_decay, update=update, has_params=True)
+        return y
+
+    def group_norm(self, x, num_groups=32, scale=True, shift=True, zero_scale_init=False, epsilon=1e-3, scope='gn'):
+        """reference convnet.py:1928-2013: per-(image, group) moments over H x W x C/num_groups in fp32, then gamma / beta; 4-D and 2-D
+        ([B, C]) inputs.  One 'gn' graph node (mcn_gn_fwd / mcn_gn_bwd) with its saved [N][G] statistics; a following relu and
+        add(skip) [-> relu] fuse into it as into batch norm.  Training and inference run the same kernel, inference on the EMA
+        shadows of gamma / beta (convnet.py:1999-2000)."""
+        trainable = self._trainable_here()
+        c = x.shape[-1]
+        h, w = (x.shape[1], x.shape[2]) if len(x.shape) > 2 else (1, 1)
+        with self.variable_scope(scope):
+            assert c // num_groups * num_groups == c, 'Number of channels must be a multiple of num_groups ({})'.format(num_groups)
+            gamma = beta = None
+            if scale:
+                gamma = self._new_variable('gamma', c, 'gamma', zeros() if zero_scale_init else ones(), trainable)
+                self._params += c
+                self._flops += h * w * c
+            if shift:
+                beta = self._new_variable('beta', c, 'beta', zeros(), trainable)
+                self._params += c
+                self._flops += h * w * c
+            for v in (gamma, beta):
+                if v is not None:
+                    self.add_to_collection('norm_variables', v)
+                    self.add_to_collection('block_{}/norm_variables'.format(self._curr_block), v)
+            name = self.scope_name()
+        y = self.graph.tensor(x.shape, x.dtype, name, self._channel_first)
+        self.graph.node('gn', [x], [y], scope=name, gamma=gamma, beta=beta, groups=int(num_groups), eps=epsilon, has_params=True)
         return y
 
     def _pool(self, op, x, side_l, stride, padding):

@@ -634,6 +634,124 @@ extern "C" int mcn_dwconv2d_wgrad(const void* x, const void* dy, float* dw, cons
     });
 }
 
+// ---- group normalisation (convnet.py:1928-2013) --------------------------------------------------------------------------------------------
+extern "C" size_t mcn_gn_workspace_bytes(int32_t N, int64_t HW, int32_t C, int32_t G) { return (N > 0 && HW > 0 && C > 0 && G > 0) ? 256 : 0; }
+extern "C" int32_t mcn_gn_resident_ok(int32_t, int32_t, int64_t, int32_t, int32_t, mcn_dtype) { return 0; }      // (the path hint is a launch shape: nothing to choose here)
+static int gn_check(const char* who, int32_t N, int64_t HW, int32_t C, int32_t G, mcn_act act, mcn_dtype dtype, int32_t path, const void* ws, size_t ws_bytes) {
+    if (N <= 0 || HW <= 0 || C <= 0 || G <= 0) return fail(MCN_E_BADARG, "%s: bad argument", who);
+    if (C % G) return fail(MCN_E_BADARG, "%s: %d channels are not a multiple of %d groups", who, C, G);
+    if (dtype != MCN_F32 && dtype != MCN_BF16 && dtype != MCN_F16) return fail(MCN_E_UNSUPPORTED, "%s: dtype %d unsupported", who, (int)dtype);
+    if (C % (dtype == MCN_F32 ? 4 : 8)) return fail(MCN_E_UNSUPPORTED, "%s: C = %d is not a multiple of the 16-byte chunk", who, C);
+    if (act != MCN_ACT_NONE && act != MCN_ACT_RELU) return fail(MCN_E_UNSUPPORTED, "%s: activation %d is not fused (none / relu)", who, (int)act);
+    if (path != 0 && path != MCN_GN_TWO_PASS && path != MCN_GN_RESIDENT) return fail(MCN_E_BADARG, "%s: path hint %d", who, path);
+    if (!ws || ws_bytes < mcn_gn_workspace_bytes(N, HW, C, G)) return fail(MCN_E_WORKSPACE, "%s: workspace too small", who);
+    if (path == MCN_GN_RESIDENT) return fail(MCN_E_UNSUPPORTED, "%s: no resident path in libmcn_cpu.so", who);
+    return MCN_OK;
+}
+extern "C" int mcn_gn_fwd(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* save_mean, float* save_invstd, int32_t N, int64_t HW,
+                          int32_t C, int32_t G, float eps, mcn_act act, mcn_dtype dtype, int32_t path, void* ws, size_t ws_bytes, void*) {
+    if (!x || !y) return fail(MCN_E_BADARG, "gn_fwd: null tensor");
+    const int rc = gn_check("gn_fwd", N, HW, C, G, act, dtype, path, ws, ws_bytes);
+    if (rc != MCN_OK) return rc;
+    return by_dtype(dtype, "gn_fwd", [&](auto s) {
+        typedef decltype(s) S;
+        typedef typename S::T T;
+        const T* xp = (const T*)x;
+        const T* sp = (const T*)skip;
+        T* yp = (T*)y;
+        const int cpg = C / G;
+#pragma omp parallel for schedule(static)
+        for (int64_t p = 0; p < (int64_t)N * G; ++p) {
+            const int64_t n = p / G;
+            const int c0 = (int)(p % G) * cpg;
+            const T* xi = xp + n * HW * C;
+            const double piv = S::ld(xi + c0);
+            double a = 0.0, b = 0.0;
+            for (int64_t r = 0; r < HW; ++r)
+                for (int c = c0; c < c0 + cpg; ++c) {
+                    const double d = (double)S::ld(xi + r * C + c) - piv;
+                    a += d;
+                    b += d * d;
+                }
+            const double m = (double)HW * cpg, dm = a / m;
+            double var = b / m - dm * dm;
+            if (var < 0.0) var = 0.0;
+            const float fmean = (float)(piv + dm), finv = (float)(1.0 / std::sqrt(var + (double)eps));
+            if (save_mean) save_mean[p] = fmean;
+            if (save_invstd) save_invstd[p] = finv;
+            for (int c = c0; c < c0 + cpg; ++c) {
+                const float sc = (gamma ? gamma[c] : 1.f) * finv, sh = (beta ? beta[c] : 0.f) - fmean * sc;
+                for (int64_t r = 0; r < HW; ++r) {
+                    const int64_t i = (n * HW + r) * C + c;
+                    float o = fmaf(S::ld(xp + i), sc, sh);
+                    if (sp) o += S::ld(sp + i);
+                    if (act == MCN_ACT_RELU) o = o > 0.f ? o : 0.f;
+                    S::st(yp + i, o);
+                }
+            }
+        }
+        return (int)MCN_OK;
+    });
+}
+extern "C" int mcn_gn_bwd(const void* dy, const void* x, const void* y, const float* gamma, const float* save_mean, const float* save_invstd, void* dx, void* dskip,
+                          float* dgamma, float* dbeta, float grad_scale, int32_t N, int64_t HW, int32_t C, int32_t G, mcn_act act, mcn_dtype dtype, int32_t path, void* ws,
+                          size_t ws_bytes, void*) {
+    if (!dy || !x || !dx || !save_mean || !save_invstd) return fail(MCN_E_BADARG, "gn_bwd: null tensor");
+    const int rc = gn_check("gn_bwd", N, HW, C, G, act, dtype, path, ws, ws_bytes);
+    if (rc != MCN_OK) return rc;
+    if (act == MCN_ACT_RELU && !y) return fail(MCN_E_BADARG, "gn_bwd: ReLU takes its mask from the stored output y");
+    return by_dtype(dtype, "gn_bwd", [&](auto s) {
+        typedef decltype(s) S;
+        typedef typename S::T T;
+        const T* dyp = (const T*)dy;
+        const T* xp = (const T*)x;
+        const T* yp = (const T*)y;
+        T* dxp = (T*)dx;
+        T* dsp = (T*)dskip;
+        const int cpg = C / G;
+        std::vector<double> pa((size_t)N * C), pb((size_t)N * C);      // per-image channel sums: sum dz, sum dz * xhat
+        auto dz = [&](int64_t i) { const float g = S::ld(dyp + i); return (act == MCN_ACT_RELU && !(S::ld(yp + i) > 0.f)) ? 0.f : g; };
+#pragma omp parallel for schedule(static)
+        for (int64_t p = 0; p < (int64_t)N * G; ++p) {
+            const int64_t n = p / G;
+            const int c0 = (int)(p % G) * cpg;
+            const float mu = save_mean[p], is = save_invstd[p];
+            double A = 0.0, B = 0.0;
+            for (int c = c0; c < c0 + cpg; ++c) {
+                double a = 0.0, b = 0.0;
+                for (int64_t r = 0; r < HW; ++r) {
+                    const int64_t i = (n * HW + r) * C + c;
+                    const float g = dz(i);
+                    a += g;
+                    b += (double)g * ((S::ld(xp + i) - mu) * is);
+                }
+                pa[n * C + c] = a;
+                pb[n * C + c] = b;
+                A += (gamma ? gamma[c] : 1.f) * a;
+                B += (gamma ? gamma[c] : 1.f) * b;
+            }
+            const float ca = (float)(A / ((double)HW * cpg)), cb = (float)(B / ((double)HW * cpg));
+            for (int c = c0; c < c0 + cpg; ++c)
+                for (int64_t r = 0; r < HW; ++r) {
+                    const int64_t i = (n * HW + r) * C + c;
+                    const float g = dz(i), xh = (S::ld(xp + i) - mu) * is;
+                    S::st(dxp + i, is * ((gamma ? gamma[c] : 1.f) * g - ca - xh * cb));
+                    if (dsp) S::st(dsp + i, g);
+                }
+        }
+        for (int c = 0; c < C; ++c) {
+            double a = 0.0, b = 0.0;
+            for (int64_t n = 0; n < N; ++n) {
+                a += pa[n * C + c];
+                b += pb[n * C + c];
+            }
+            if (dbeta) dbeta[c] = (float)a * grad_scale;
+            if (dgamma) dgamma[c] = (float)b * grad_scale;
+        }
+        return (int)MCN_OK;
+    });
+}
+
 // ---- element-wise ------------------------------------------------------------------------------------------------------------------------
 template <typename S, typename F>
 static int map_n(int64_t n, F&& f) {

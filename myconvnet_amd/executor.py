@@ -87,6 +87,8 @@ class Lowering(object):
             elif n.op == 'bn':
                 x = n.inputs[0]
                 need = max(need, lib.mcn_bn_workspace_bytes(x.numel // x.shape[-1], x.shape[-1]))
+            elif n.op == 'gn':
+                need = max(need, lib.mcn_gn_workspace_bytes(*self._gn_dims(n)))
             elif n.op == 'fc':
                 x = n.inputs[0]
                 need = max(need, lib.mcn_fc_workspace_bytes(x.shape[0], x.shape[1], n.outputs[0].shape[1], self.dt))
@@ -868,6 +870,53 @@ class Lowering(object):
                          b.grad.data_ptr() if b is not None and b.trainable else 0, gs, M, C, act, MCN_DT[x.dtype],
                          self.ws_ptr, self.ws_bytes)
         self.contribute_via_scratch(x, emit)
+        if post:
+            self.bwd.add(lib.mcn_accumulate, *post)
+        self.bwd.mark(('grad_ready', tuple(v.name for v in (g, b) if v is not None and v.trainable)))
+
+    # ---- group norm (convnet.py:1928-2013) ----------------------------------------------------------------------------------
+    def _gn_dims(self, n):
+        """(N, HW, C, G) of a group norm node: 4-D NHWC or the reference's 2-D [B, C] case (HW = 1)"""
+        x = n.inputs[0]
+        assert x.cs == x.shape[-1], 'group norm needs a dense channel axis'
+        return x.shape[0], x.numel // (x.shape[0] * x.shape[-1]), x.shape[-1], n.attrs['groups']
+
+    def fwd_gn(self, n):
+        """Training and inference run the same kernel — the statistics are per image; inference reads the EMA shadows of gamma / beta
+        (vptr; convnet.py:1999-2000).  No cross-rank statistics, hence no data-parallel exchange; path 0 = the library's measured choice."""
+        x, y = n.inputs[0], n.outputs[0]
+        a = n.attrs
+        skip = a.get('skip')
+        st = a['saved']
+        self.fwd.add(lib.mcn_gn_fwd, x.buf.data_ptr(), self.vptr(a['gamma']), self.vptr(a['beta']), ptr(skip.buf) if skip else 0, y.buf.data_ptr(),
+                     st['mean'].data_ptr() if self.train else 0, st['invstd'].data_ptr() if self.train else 0, *self._gn_dims(n), float(a['eps']),
+                     a.get('act', 0), MCN_DT[x.dtype], 0, self.ws_ptr, self.ws_bytes)
+
+    def bwd_gn(self, n):
+        """The ReLU mask comes from the stored output; the skip gradient takes the generic contribute / scratch route (the BN-only
+        shortcuts — deferred dskip, byte masks, dgrad epilogue sums, SE routes — key on op == 'bn')."""
+        x, y = n.inputs[0], n.outputs[0]
+        a = n.attrs
+        skip = a.get('skip')
+        st = a['saved']
+        g, b = a['gamma'], a['beta']
+        dskip_ptr, post = 0, None
+        if skip is not None and skip.needs_grad:
+            if skip.id not in self.written:
+                self.written.add(skip.id)
+                dskip_ptr = skip.grad.data_ptr()
+            else:
+                s = self.scratch_like(skip, 'gn_dskip')
+                dskip_ptr = s.data_ptr()
+                post = (skip.grad.data_ptr(), s.data_ptr(), skip.grad.numel(), MCN_DT[skip.dtype])
+        # (a frozen block's gn still runs when its skip branch needs dz: dx then goes to scratch)
+        emit = lambda dst: self.bwd.add(lib.mcn_gn_bwd, y.grad.data_ptr(), x.buf.data_ptr(), y.buf.data_ptr(), self.vptr(g), st['mean'].data_ptr(), st['invstd'].data_ptr(),
+                                        dst, dskip_ptr, g.grad.data_ptr() if g is not None and g.trainable else 0, b.grad.data_ptr() if b is not None and b.trainable else 0,
+                                        1.0 / self.loss_scale, *(list(self._gn_dims(n)) + [a.get('act', 0), MCN_DT[x.dtype], 0, self.ws_ptr, self.ws_bytes]))
+        if x.needs_grad:
+            self.contribute_via_scratch(x, emit)
+        else:
+            emit(self.scratch_like(x, 'gn_dx').data_ptr())
         if post:
             self.bwd.add(lib.mcn_accumulate, *post)
         self.bwd.mark(('grad_ready', tuple(v.name for v in (g, b) if v is not None and v.trainable)))
