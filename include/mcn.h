@@ -394,6 +394,43 @@ int mcn_gn_bwd(const void* dy, const void* x, const void* y, const float* gamma,
                void* dx, void* dskip, float* dgamma, float* dbeta, float grad_scale, int32_t N, int64_t HW, int32_t C, int32_t G,
                mcn_act act, mcn_dtype dtype, int32_t path, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- weight standardisation --------------------------------------------------------------
+ * replaces the weight_standardization branch of ConvNet.weight_variable (reference convnet.py:1410-1419; conv_layer(ws=True) in
+ * models/resnet_v1_5_wsgn.py and models/efficientnet_wsgn.py).  An fp32 HWIO filter is the row-major matrix w[K][C], K = KH*KW*Cin rows,
+ * C = Cout columns; the moments run over every axis but the last (convnet.py:1411), per column c:
+ *   m = mean_k w,  s = sqrt(mean_k (w - m)^2)  (biased, no epsilon inside the root: convnet.py:1412-1414),
+ *   w_hat = (w - m) / (s + eps)                (epsilon OUTSIDE the root: convnet.py:1415-1419; the reference's eps is 1e-5).
+ * Always fp32: the per-use cast to the activation type (convnet.py:1421-1422) happens behind it, in the pack / the conv entry points, which
+ * take w_hat wherever they take the master.  In evaluation the caller points the jobs at the EMA shadows (convnet.py:1406-1408: the cond
+ * comes before the standardisation).
+ *
+ * Forward, batched (convnet.py:1410-1419 for every standardised filter of a model at once): like the pack table above, the caller builds an
+ * opaque descriptor table on the host once, uploads it once, and runs it whenever the masters changed — two launches whatever the number
+ * of jobs:
+ *   mcn_ws_table_build(jobs, n, host_table, mcn_ws_table_bytes(jobs, n), &ndesc);  copy host_table to the device;
+ *   mcn_ws_fwd_run(dev_table, ndesc, eps, workspace, mcn_ws_fwd_workspace_bytes(jobs, n), stream)
+ * stats receives m in [0][C] and s in [1][C] (kept for mcn_ws_bwd).  K == 1 (s = 0, the reference's gradient is undefined) and NULL
+ * pointers: MCN_E_BADARG; a short table buffer or workspace: MCN_E_WORKSPACE.  Any C >= 1, K >= 2; rows that are not 16-byte aligned
+ * (C % 4 != 0) take a scalar-column path.  Deterministic (no atomics): a repeated run is bit-identical and a job's result does not depend on
+ * the other jobs of the table.
+ *
+ * Backward (tf.gradients through convnet.py:1410-1419), one call per filter behind its mcn_conv2d_wgrad: with r = 1 / (s + eps)
+ *   dw = r * (dw_hat - mean_k dw_hat) - w_hat * mean_k(dw_hat * w_hat) / s
+ * from dw_hat, w_hat and the saved stats (the master is not read again).  dw may alias dw_hat (in place).  Two launches, no hidden sync. */
+typedef struct {
+    const float* w;  /* device pointer: fp32 [K][C] master (or EMA shadow) */
+    float* w_hat;    /* device pointer: fp32 [K][C] */
+    float* stats;    /* device pointer: fp32 [2][C]: m, s */
+    int32_t K, C;
+} mcn_ws_job;
+size_t mcn_ws_table_bytes(const mcn_ws_job* jobs, int32_t njobs);
+int mcn_ws_table_build(const mcn_ws_job* jobs, int32_t njobs, void* host_table, size_t host_table_bytes, int32_t* ndesc);
+size_t mcn_ws_fwd_workspace_bytes(const mcn_ws_job* jobs, int32_t njobs);
+int mcn_ws_fwd_run(const void* dev_table, int32_t ndesc, float eps, void* workspace, size_t workspace_bytes, void* stream);
+size_t mcn_ws_bwd_workspace_bytes(int32_t K, int32_t C);
+int mcn_ws_bwd(const float* dw_hat, const float* w_hat, const float* stats, float* dw, int32_t K, int32_t C, float eps, void* workspace,
+               size_t workspace_bytes, void* stream);
+
 /* ---- element-wise -----------------------------------------------------------------------
  * tf.nn.relu / ReluGrad (convnet.py:2537); x + skip followed by relu (convnet.py:2511, 2537). */
 int mcn_relu_fwd(const void* x, void* y, int64_t n, mcn_dtype dtype, void* stream);

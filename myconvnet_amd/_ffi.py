@@ -40,6 +40,20 @@ class PackJob(ctypes.Structure):
     _fields_ = [('w_hwio', c_void_p), ('packed', c_void_p), ('geom', ConvGeom), ('op', c_int32), ('reserved', c_int32)]
 
 
+class WsJob(ctypes.Structure):
+    _fields_ = [('w', c_void_p), ('w_hat', c_void_p), ('stats', c_void_p), ('K', c_int32), ('C', c_int32)]
+
+
+def ws_table(jobs):
+    """Host descriptor table of the batched weight standardisation (mcn_ws_table_build): (table bytes, ndesc, workspace bytes)"""
+    arr = (WsJob * len(jobs))(*jobs)
+    nbytes = int(lib.mcn_ws_table_bytes(arr, len(jobs)))
+    host = (ctypes.c_char * max(nbytes, 1))()
+    ndesc = c_int32(0)
+    check(lib.mcn_ws_table_build(arr, len(jobs), ctypes.cast(host, c_void_p), nbytes, ctypes.byref(ndesc)))
+    return bytearray(host.raw[:nbytes]), ndesc.value, int(lib.mcn_ws_fwd_workspace_bytes(arr, len(jobs)))
+
+
 # name -> (restype, argtypes); every symbol include/mcn.h declares
 SIGNATURES = {
     'mcn_version': (c_int, []),
@@ -146,6 +160,12 @@ SIGNATURES = {
     'mcn_gn_resident_ok': (c_int32, [c_int32, c_int32, c_int64, c_int32, c_int32, c_int]),
     'mcn_gn_fwd': (c_int, [c_void_p] * 7 + [c_int32, c_int64, c_int32, c_int32, c_float, c_int, c_int, c_int32, c_void_p, c_size_t, c_void_p]),
     'mcn_gn_bwd': (c_int, [c_void_p] * 10 + [c_float, c_int32, c_int64, c_int32, c_int32, c_int, c_int, c_int32, c_void_p, c_size_t, c_void_p]),
+    'mcn_ws_table_bytes': (c_size_t, [ctypes.POINTER(WsJob), c_int32]),
+    'mcn_ws_table_build': (c_int, [ctypes.POINTER(WsJob), c_int32, c_void_p, c_size_t, ctypes.POINTER(c_int32)]),
+    'mcn_ws_fwd_workspace_bytes': (c_size_t, [ctypes.POINTER(WsJob), c_int32]),
+    'mcn_ws_fwd_run': (c_int, [c_void_p, c_int32, c_float, c_void_p, c_size_t, c_void_p]),
+    'mcn_ws_bwd_workspace_bytes': (c_size_t, [c_int32, c_int32]),
+    'mcn_ws_bwd': (c_int, [c_void_p] * 4 + [c_int32, c_int32, c_float, c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -7,7 +7,10 @@ reference's ConvNet needs only its `tf.*` calls swapped for the methods here (IN
 What differs by design: there is no TF session — `_build_model` records a static graph once, and
 `compile()` turns it into flat lists of HIP launches (graph.py / executor.py).
 
-Not built (raise NotImplementedError): depthwise conv, weight standardisation, the normalization()
+Weight standardisation (conv_layer(ws=True), reference convnet.py:1410-1419) is built for ordinary convolutions: the
+executor standardises every such filter in one batched launch pair per step and the conv reads w_hat in place of the master.
+
+Not built (raise NotImplementedError): weight standardisation of depthwise filters and of fc_layer, the normalization()
 dispatcher for anything but 'batch' (group_norm itself is built: a model calls it from _build_model),
 augmentation, dropout rate > 0, transposed conv / upsampling (SURVEY.md §8f "next" rows).
 """
@@ -212,14 +215,15 @@ class ConvNet(object):
         return v
 
     def weight_variable(self, shape, initializer=None, weight_standardization=False, paddings=((0, 0), (0, 0)), name='weights'):
-        """reference convnet.py:1382-1431 (fp32 master on the parameter device, EMA shadow, per-use cast)."""
-        if weight_standardization:
-            raise NotImplementedError('weight standardisation is outside the built path')
+        """reference convnet.py:1382-1431 (fp32 master on the parameter device, EMA shadow, per-use cast).  weight_standardization
+        (convnet.py:1410-1419) marks the variable; conv_layer hands the mark to its conv node and the executor standardises the filter
+        (master in training, EMA shadow in evaluation) in front of the per-use cast."""
         if any(p > 0 for pp in paddings for p in pp):
             raise NotImplementedError('kernel_paddings are outside the built path')
         if self._dropout_weights and self._parameters.get('dropout_rate', 0.0) > 0.0:
             raise NotImplementedError('weight dropout is outside the built path')
         v = self._new_variable(name, shape, 'weight', initializer or he_normal(), self._trainable_here())
+        v.ws = bool(weight_standardization)
         self.add_to_collection('weight_variables', v)
         self.add_to_collection('block_{}/weight_variables'.format(self._curr_block), v)
         return v
@@ -584,7 +588,7 @@ class ConvNet(object):
         y = self.graph.tensor((n, oh, ow, out_channels), x.dtype, name + '/conv', self._channel_first)
         geom = _ffi.conv_geom(n, h, w, cin, out_channels, kernel[0], kernel[1], stride[0], stride[1], dilation[0], dilation[1],
                               (pt, pb, pl, pr), x.cs)
-        self.graph.node('conv', [x], [y], scope=name, geom=geom, w=wv, b=bv, has_params=True)
+        self.graph.node('conv', [x], [y], scope=name, geom=geom, w=wv, b=bv, ws=wv.ws, has_params=True)
         # the reference's report uses np.ceil on floats for out_size; identical for integer inputs (convnet.py:1626-1664)
         flops = oh * ow * kernel[0] * kernel[1] * cin * out_channels
         params = kernel[0] * kernel[1] * cin * out_channels
@@ -598,6 +602,9 @@ class ConvNet(object):
     def _depthwise_conv_layer(self, x, kernel, stride, out_channels, padding, biased, scope, dilation, ws, kernel_paddings,
                               weight_initializer, bias_initializer):
         """reference convnet.py:1634-1650 -> tf.nn.depthwise_conv2d (:1645), filter [kh, kw, cin, multiplier]."""
+        if ws:
+            raise NotImplementedError('weight standardisation of a depthwise filter is outside the built path (the host plumbing of the '
+                                      'dwconv node is missing; mcn_ws_* itself handles its [KH*KW*Cin][multiplier] shape)')
         n, h, w, cin = x.shape
         mult = max(out_channels // cin, 1)
         if biased and out_channels != cin * mult:             # (tf.nn.bias_add would refuse the shapes: convnet.py:1679,1694)
@@ -651,6 +658,9 @@ class ConvNet(object):
 
     def fc_layer(self, x, out_dim, biased=True, scope=None, ws=False, weight_initializer=None, bias_initializer=None, verbose=False):
         """reference convnet.py:1708-1755 -> tf.matmul(x, W) + b."""
+        if ws:
+            raise NotImplementedError('weight standardisation of fc_layer weights is outside the built path (the fc node does not read '
+                                      'a standardised copy yet; mcn_ws_* itself handles its [in_dim][out_dim] shape)')
         in_dim = int(x.shape[-1])
         with self.variable_scope(scope) if scope is not None else nullcontext():
             wv = self.weight_variable([in_dim, out_dim], initializer=weight_initializer, weight_standardization=ws)

@@ -634,6 +634,60 @@ extern "C" int mcn_dwconv2d_wgrad(const void* x, const void* dy, float* dw, cons
     });
 }
 
+// ---- weight standardisation (convnet.py:1410-1419): a descriptor is the job itself ---------------------------------------------------------
+extern "C" size_t mcn_ws_table_bytes(const mcn_ws_job* jobs, int32_t njobs) { return (jobs && njobs > 0) ? (size_t)njobs * sizeof(mcn_ws_job) : 0; }
+extern "C" size_t mcn_ws_fwd_workspace_bytes(const mcn_ws_job* jobs, int32_t njobs) { return (jobs && njobs > 0) ? (size_t)njobs * 256 : 0; }
+extern "C" int mcn_ws_table_build(const mcn_ws_job* jobs, int32_t njobs, void* host_table, size_t bytes, int32_t* ndesc) {
+    if (!jobs || !host_table || !ndesc || njobs <= 0) return fail(MCN_E_BADARG, "ws_table_build: bad argument");
+    for (int i = 0; i < njobs; ++i) {
+        if (!jobs[i].w || !jobs[i].w_hat || !jobs[i].stats) return fail(MCN_E_BADARG, "ws_table_build: job %d has a null pointer", i);
+        if (jobs[i].C < 1 || jobs[i].K < 1) return fail(MCN_E_BADARG, "ws_table_build: job %d has K = %d, C = %d", i, jobs[i].K, jobs[i].C);
+        if (jobs[i].K == 1) return fail(MCN_E_BADARG, "ws_table_build: job %d has K = 1: the deviation of one row is 0 and its gradient undefined", i);
+    }
+    if (bytes < mcn_ws_table_bytes(jobs, njobs)) return fail(MCN_E_WORKSPACE, "ws_table_build: table buffer too small");
+    memcpy(host_table, jobs, (size_t)njobs * sizeof(mcn_ws_job));
+    *ndesc = njobs;
+    return MCN_OK;
+}
+extern "C" int mcn_ws_fwd_run(const void* table, int32_t ndesc, float eps, void* ws, size_t ws_bytes, void*) {
+    if (!table || ndesc <= 0) return fail(MCN_E_BADARG, "ws_fwd_run: null or empty table");
+    if (!ws || ws_bytes < (size_t)ndesc * 256) return fail(MCN_E_WORKSPACE, "ws_fwd_run: workspace too small");
+    const mcn_ws_job* jobs = (const mcn_ws_job*)table;
+    for (int i = 0; i < ndesc; ++i) {
+        const mcn_ws_job& j = jobs[i];
+#pragma omp parallel for schedule(static)
+        for (int c = 0; c < j.C; ++c) {
+            double a = 0.0, b = 0.0;
+            for (int k = 0; k < j.K; ++k) a += j.w[(size_t)k * j.C + c];
+            const double m = a / j.K;
+            for (int k = 0; k < j.K; ++k) b += (j.w[(size_t)k * j.C + c] - m) * (j.w[(size_t)k * j.C + c] - m);
+            const float fm = (float)m, s = (float)std::sqrt(b / j.K), r = 1.f / (s + eps);
+            j.stats[c] = fm;
+            j.stats[j.C + c] = s;
+            for (int k = 0; k < j.K; ++k) j.w_hat[(size_t)k * j.C + c] = (j.w[(size_t)k * j.C + c] - fm) * r;
+        }
+    }
+    return MCN_OK;
+}
+extern "C" size_t mcn_ws_bwd_workspace_bytes(int32_t K, int32_t C) { return (K > 0 && C > 0) ? 256 : 0; }
+extern "C" int mcn_ws_bwd(const float* dw_hat, const float* w_hat, const float* stats, float* dw, int32_t K, int32_t C, float eps, void* ws, size_t ws_bytes, void*) {
+    if (!dw_hat || !w_hat || !stats || !dw) return fail(MCN_E_BADARG, "ws_bwd: null tensor");
+    if (K < 1 || C < 1) return fail(MCN_E_BADARG, "ws_bwd: K = %d, C = %d", K, C);
+    if (K == 1) return fail(MCN_E_BADARG, "ws_bwd: K = 1: the deviation of one row is 0 and its gradient undefined");
+    if (!ws || ws_bytes < mcn_ws_bwd_workspace_bytes(K, C)) return fail(MCN_E_WORKSPACE, "ws_bwd: workspace too small");
+#pragma omp parallel for schedule(static)
+    for (int c = 0; c < C; ++c) {
+        double a = 0.0, b = 0.0;
+        for (int k = 0; k < K; ++k) {
+            a += dw_hat[(size_t)k * C + c];
+            b += (double)dw_hat[(size_t)k * C + c] * w_hat[(size_t)k * C + c];
+        }
+        const float s = stats[C + c], r = 1.f / (s + eps), ma = (float)(a / K), mb = (float)(b / K / s);
+        for (int k = 0; k < K; ++k) dw[(size_t)k * C + c] = r * (dw_hat[(size_t)k * C + c] - ma) - w_hat[(size_t)k * C + c] * mb;      // (in place: element k is read before it is written)
+    }
+    return MCN_OK;
+}
+
 // ---- group normalisation (convnet.py:1928-2013) --------------------------------------------------------------------------------------------
 extern "C" size_t mcn_gn_workspace_bytes(int32_t N, int64_t HW, int32_t C, int32_t G) { return (N > 0 && HW > 0 && C > 0 && G > 0) ? 256 : 0; }
 extern "C" int32_t mcn_gn_resident_ok(int32_t, int32_t, int64_t, int32_t, int32_t, mcn_dtype) { return 0; }      // (the path hint is a launch shape: nothing to choose here)

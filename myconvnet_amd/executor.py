@@ -10,6 +10,9 @@ from ._ffi import lib
 from .graph import MCN_DT, TORCH_DT, Program, ptr
 
 
+WS_EPS = 1e-5        # weight standardisation: weights / (std + 1e-5), reference convnet.py:1419
+
+
 def _env_flag(name, default):
     """Experiment switch: MCN_<NAME>=0/1 overrides a lowering default (an explicit model kwarg still wins)."""
     e = os.environ.get(name)
@@ -71,8 +74,22 @@ class Lowering(object):
             return 0
         return var.data.data_ptr() if self.train else var.ema.data_ptr()
 
+    def ws_convs(self):
+        """conv nodes whose filter is standardised (conv_layer(ws=True), reference convnet.py:1410-1419)"""
+        return [n for n in self.g.nodes if n.op == 'conv' and n.attrs.get('ws')]
+
+    @staticmethod
+    def _ws_dims(n):
+        """(K, C) of a conv node's HWIO filter seen as the matrix [KH*KW*Cin][Cout]"""
+        shape = n.attrs['w'].shape
+        return int(shape[0] * shape[1] * shape[2]), int(shape[3])
+
     def workspace_bytes(self):
         need = 4096
+        wsn = self.ws_convs()
+        if wsn:
+            jobs = (_ffi.WsJob * len(wsn))(*[_ffi.WsJob(0, 0, 0, *self._ws_dims(n)) for n in wsn])
+            need = max(need, lib.mcn_ws_fwd_workspace_bytes(jobs, len(wsn)), *[lib.mcn_ws_bwd_workspace_bytes(*self._ws_dims(n)) for n in wsn])
         for n in self.g.nodes:
             if n.op == 'conv':
                 for op in (_ffi.CONV_FWD, _ffi.CONV_DGRAD, _ffi.CONV_WGRAD):
@@ -200,13 +217,14 @@ class Lowering(object):
             shared = torch.zeros(max(total, 256), dtype=torch.uint8, device=self.g.device)
             self.model._packed_store = shared
         self.packed_ptr = {k: shared.data_ptr() + o for k, o in offs.items()}
+        self.plan_weight_standardization()             # (first in the prepack program: the pair rebuilds and the pack below read w_hat)
         for n in self.g.nodes:
             if n.op != 'conv':
                 continue
             if 'geom_orig' in n.attrs:
                 # pixel-pair form (convnet._plan_pixel_pairs): the paired filter is rebuilt from the master (or its EMA shadow) in front
                 # of the batched pack
-                self.prepack.add(lib.mcn_conv2d_pair_weights, self.vptr(n.attrs['w']), self.pair_buffers(n)[0].data_ptr(), ctypes.byref(n.attrs['geom_orig']), self.dt)
+                self.prepack.add(lib.mcn_conv2d_pair_weights, self.wflat(n), self.pair_buffers(n)[0].data_ptr(), ctypes.byref(n.attrs['geom_orig']), self.dt)
             for op in (_ffi.CONV_FWD, _ffi.CONV_DGRAD):
                 if (id(n), op) in self.packed_ptr:
                     jobs.append(_ffi.PackJob(self.wsrc(n), self.packed_ptr[(id(n), op)], n.attrs['geom'], op, 0))
@@ -220,6 +238,45 @@ class Lowering(object):
         self.pack_table = torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(self.g.device)
         self.prepack.add(lib.mcn_conv2d_pack_run, self.pack_table.data_ptr(), ndesc.value, self.dt)
 
+    def plan_weight_standardization(self):
+        """Weight standardisation (reference convnet.py:1410-1419) of every conv_layer(ws=True) filter in ONE batched call at the head of the
+        prepack program (mcn_ws_fwd_run: two launches whatever the number of layers): w_hat and the (m, s) statistics live in two stores
+        shared by the train and eval lowerings like the packed operands (each lowering runs its own table — masters vs EMA shadows,
+        convnet.py:1406-1408 — before its forward pass); wflat() then hands w_hat to everything that read the master."""
+        self.ws_hat, self.ws_stats = {}, {}
+        nodes = self.ws_convs()
+        if not nodes:
+            return
+        offs, total, stotal = {}, 0, 0
+        for n in nodes:
+            K, C = self._ws_dims(n)
+            offs[id(n)] = (total, stotal)
+            total += (K * C + 63) // 64 * 64
+            stotal += (2 * C + 63) // 64 * 64
+        shared = getattr(self.model, '_ws_store', None)
+        if shared is None or shared[0].numel() < total or shared[1].numel() < stotal:
+            shared = (torch.zeros(total, dtype=torch.float32, device=self.g.device), torch.zeros(stotal, dtype=torch.float32, device=self.g.device))
+            self.model._ws_store = shared
+        jobs = []
+        for n in nodes:
+            self.ws_hat[id(n)] = shared[0].data_ptr() + 4 * offs[id(n)][0]
+            self.ws_stats[id(n)] = shared[1].data_ptr() + 4 * offs[id(n)][1]
+            jobs.append(_ffi.WsJob(self.vptr(n.attrs['w']), self.ws_hat[id(n)], self.ws_stats[id(n)], *self._ws_dims(n)))
+        table, ndesc, nbytes = _ffi.ws_table(jobs)
+        assert nbytes <= self.ws_bytes
+        self.ws_table = torch.frombuffer(table, dtype=torch.uint8).to(self.g.device)
+        self.prepack.add(lib.mcn_ws_fwd_run, self.ws_table.data_ptr(), ndesc, WS_EPS, self.ws_ptr, self.ws_bytes)
+
+    def wflat(self, n):
+        """fp32 HWIO filter of conv node n in its original geometry: the variable (master / EMA shadow), or its standardised form"""
+        return self.ws_hat.get(id(n)) or self.vptr(n.attrs['w'])
+
+    def _ws_bwd_args(self, n):
+        """mcn_ws_bwd in place on w.grad: what the wgrad (and the pair fold) left there is dw_hat, the gradient of the standardised filter;
+        the optimizer, the decay terms, clipping and the all-reduce behind the grad_ready mark see the master's gradient"""
+        g = n.attrs['w'].grad.data_ptr()
+        return [g, self.ws_hat[id(n)], self.ws_stats[id(n)], g] + list(self._ws_dims(n)) + [WS_EPS]
+
     def wp(self, n, op):
         return self.packed_ptr.get((id(n), op), 0)
 
@@ -232,10 +289,11 @@ class Lowering(object):
         return n.attrs['pair_buf']
 
     def wsrc(self, n):
-        """fp32 HWIO filter the conv entry points read for node n: the variable (master / EMA shadow), or its paired form"""
+        """fp32 HWIO filter the conv entry points read for node n: the variable (master / EMA shadow) or its standardised form, or the
+        paired form of either"""
         if 'geom_orig' in n.attrs:
             return self.pair_buffers(n)[0].data_ptr()
-        return self.vptr(n.attrs['w'])
+        return self.wflat(n)
 
     def autotune(self, reps=3):
         """Measure, don't guess: time every tile candidate of every conv launch of this lowering on the GPU (HIP events
@@ -412,6 +470,7 @@ class Lowering(object):
         gm = self.op_geom(n, _ffi.CONV_DGRAD)
         gw = self.op_geom(n, _ffi.CONV_WGRAD)
         w, b = n.attrs['w'], n.attrs.get('b')
+        w_f32 = self.ws_hat.get(id(n)) or w.data.data_ptr()      # (dgrad runs on what the forward ran on)
         gs = 1.0 / self.loss_scale
         def emit_wgrad():
             if not w.trainable:
@@ -424,11 +483,15 @@ class Lowering(object):
                                   self.ws2.numel() * 4)
                 if paired:
                     self.bwd.add_side(lib.mcn_conv2d_pair_wgrad_fold, dw_ptr, w.grad.data_ptr(), ctypes.byref(n.attrs['geom_orig']), self.dt)
+                if n.attrs.get('ws'):
+                    self.bwd.add_side(lib.mcn_ws_bwd, *self._ws_bwd_args(n), self.ws2.data_ptr(), self.ws2.numel() * 4)
             else:
                 self.bwd.add(lib.mcn_conv2d_wgrad, x.buf.data_ptr(), y.grad.data_ptr(), dw_ptr,
                              b.grad.data_ptr() if b is not None else 0, ctypes.byref(gw), gs, self.dt, _ffi.NHWC, self.ws_ptr, self.ws_bytes)
                 if paired:
                     self.bwd.add(lib.mcn_conv2d_pair_wgrad_fold, dw_ptr, w.grad.data_ptr(), ctypes.byref(n.attrs['geom_orig']), self.dt)
+                if n.attrs.get('ws'):
+                    self.bwd.add(lib.mcn_ws_bwd, *self._ws_bwd_args(n), self.ws_ptr, self.ws_bytes)
             self.bwd.mark(('grad_ready', tuple(v.name for v in (w, b) if v is not None)))
 
         # With the side stream the wgrad is enqueued AFTER the dgrad: its start event then sits behind the dgrad, so the
@@ -453,23 +516,23 @@ class Lowering(object):
                     cand.append(int(lib.mcn_conv2d_dgrad_bnred_rows(ctypes.byref(gm), self.dt)))
                 gm.tile = keep
                 pa['bwd_red'] = (torch.zeros((max(cand), 2, x.shape[-1]), dtype=torch.float32, device=self.g.device), gm, n)
-                self.bwd.add(lib.mcn_conv2d_dgrad_addmasked_bnred, y.grad.data_ptr(), w.data.data_ptr(), self.wp(n, _ffi.CONV_DGRAD), x.grad.data_ptr(), lazy[0], lazy[1],
+                self.bwd.add(lib.mcn_conv2d_dgrad_addmasked_bnred, y.grad.data_ptr(), w_f32, self.wp(n, _ffi.CONV_DGRAD), x.grad.data_ptr(), lazy[0], lazy[1],
                              red.inputs[0].buf.data_ptr(), pa['relu_mask'].data_ptr(), pa['bwd_red'][0].data_ptr(), ctypes.byref(gm), self.dt, _ffi.NHWC,
                              self.ws_ptr, self.ws_bytes)
                 pa['bwd_red_done'] = True
             else:
-                self.bwd.add(lib.mcn_conv2d_dgrad_addmasked, y.grad.data_ptr(), w.data.data_ptr(), self.wp(n, _ffi.CONV_DGRAD), x.grad.data_ptr(), lazy[0], lazy[1],
+                self.bwd.add(lib.mcn_conv2d_dgrad_addmasked, y.grad.data_ptr(), w_f32, self.wp(n, _ffi.CONV_DGRAD), x.grad.data_ptr(), lazy[0], lazy[1],
                              ctypes.byref(gm), self.dt, _ffi.NHWC, self.ws_ptr, self.ws_bytes)
         elif x.needs_grad and x.producer is not None and x.producer.op == 'bn' and x.producer.attrs.get('bwd_red', (None, None, None))[2] is n:
             # x = relu(bn(u)), read by this conv only: the epilogue also leaves the BN backward's sums (bwd_bn then runs its apply pass only)
             pa = x.producer.attrs
             assert x.id not in self.written and gm is pa['bwd_red'][1]
             self.written.add(x.id)
-            self.bwd.add(lib.mcn_conv2d_dgrad_bnred, y.grad.data_ptr(), w.data.data_ptr(), self.wp(n, _ffi.CONV_DGRAD), x.grad.data_ptr(), x.producer.inputs[0].buf.data_ptr(),
+            self.bwd.add(lib.mcn_conv2d_dgrad_bnred, y.grad.data_ptr(), w_f32, self.wp(n, _ffi.CONV_DGRAD), x.grad.data_ptr(), x.producer.inputs[0].buf.data_ptr(),
                          pa['relu_mask'].data_ptr(), pa['bwd_red'][0].data_ptr(), ctypes.byref(gm), self.dt, _ffi.NHWC, self.ws_ptr, self.ws_bytes)
             pa['bwd_red_done'] = True
         elif x.needs_grad:
-            self.contribute(x, lambda dst, acc: self.bwd.add(lib.mcn_conv2d_dgrad, y.grad.data_ptr(), w.data.data_ptr(), self.wp(n, _ffi.CONV_DGRAD), dst,
+            self.contribute(x, lambda dst, acc: self.bwd.add(lib.mcn_conv2d_dgrad, y.grad.data_ptr(), w_f32, self.wp(n, _ffi.CONV_DGRAD), dst,
                                                              ctypes.byref(gm), acc, self.dt, _ffi.NHWC, self.ws_ptr, self.ws_bytes))
         if late:
             emit_wgrad()
