@@ -431,6 +431,52 @@ size_t mcn_ws_bwd_workspace_bytes(int32_t K, int32_t C);
 int mcn_ws_bwd(const float* dw_hat, const float* w_hat, const float* stats, float* dw, int32_t K, int32_t C, float eps, void* workspace,
                size_t workspace_bytes, void* stream);
 
+/* ---- CBAM attention tail ------------------------------------------------------------------
+ * replaces the tail of ResNetCBAM._res_unit (reference models/resnet_v2_d_cbam.py:159-165): x * _channel_mask(x) (:172-197), then
+ * * _spatial_mask(.) (:199-211).  x, y: [N][H][W][C] NHWC dense in `dtype`, HW = H*W, C a multiple of the 16-byte chunk (else
+ * MCN_E_UNSUPPORTED); `round` = one rounding to `dtype`; sums in fp32.  NULL tensors and a bad kernel size: MCN_E_BADARG; a short workspace:
+ * MCN_E_WORKSPACE.  No atomics: a repeated call is bit-identical.
+ *
+ * mcn_global_avgmax_pool_fwd (tf.reduce_mean / tf.reduce_max over H, W, :176-177), one read of x:
+ *   pools[0][n][c] = round(mean_hw x),  pools[1][n][c] = max_hw x          — ONE [2][N][C] tensor, i.e. the [2N][C] rows the shared MLP
+ *   (fc1 -> relu -> fc2 under reuse_variables(), :179-190) runs on once.   workspace: mcn_global_avgmax_pool_workspace_bytes(N, HW, C).
+ * mcn_pair_sigmoid_fwd (:192): cm[n][c] = round(sigmoid(a[n][c] + a[N + n][c])), a = the MLP's [2N][C] output.
+ * mcn_pair_sigmoid_bwd: da[n][c] = da[N + n][c] = round(dcm * cm * (1 - cm)).
+ * mcn_cbam_chpool_fwd (tf.reduce_mean / tf.reduce_max over C + tf.concat, :202-204), one read of x:
+ *   xp = round(x * cm[n][c]) (the product of :161, held in registers, never stored)
+ *   s[n][p][0] = round(mean_c xp),  s[n][p][1] = max_c xp                  — s: [N][H][W][2]
+ * mcn_cbam_apply_fwd (conv_layer(kernel, 1, 1, SAME, biased) + sigmoid + the product of :165), one read of x, one write:
+ *   t = round(conv_KxK_SAME(s, round(w)) + b)   w: fp32 [K][K][2][1] master, rounded per use (convnet.py:1421); b: fp32 [1] (may be NULL)
+ *   sm[n][p] = round(sigmoid(t))                sm: [N][H][W]
+ *   y = round(xp * sm[n][p])                    K odd, <= 7 (the reference uses 7); W <= 512 (else MCN_E_UNSUPPORTED)
+ *
+ * mcn_cbam_bwd: the gradient TensorFlow takes through chpool + apply, given dy; xp is recomputed bit for bit, so the indicator of
+ * reduce_max is the exact comparison value == stored max, and the gradient is split EQUALLY among ties (indicator / number of ties):
+ *   dsm[p] = sum_c dy * xp,  dt = dsm * sm * (1 - sm)
+ *   dw = grad_scale * sum_{n,p} dt[p] * s[p + tap],  db = grad_scale * sum dt     (fp32; two-stage fixed-order sums; either may be NULL)
+ *   ds[p][j] = sum_tap dt[p - tap] * round(w)[tap][j]
+ *   dxp[c] = dy[c] * sm + ds[p][0] / C + [xp[c] == s[p][1]] * ds[p][1] / ties(p)
+ *   dx = round(dxp * cm),  dcm[n][c] = round(sum_p dxp * x)                     dcm: [N][C] in `dtype`
+ * pools (may be NULL, then ties must be too): the forward's [2][N][C]; ties[n][c] (fp32) then receives #{p : x == pools[1][n][c]}, counted
+ * in the same pass over x, for mcn_global_avgmax_pool_bwd.  Three passes over the full-size tensors (2 reads, 2 reads + the write of dx);
+ * workspace: mcn_cbam_workspace_bytes(N, H, W, C, K).
+ * mcn_global_avgmax_pool_bwd, once the MLP's backward has delivered dpool [2][N][C]:
+ *   dx (+)= dpool[0][n][c] / HW + [x == pools[1][n][c]] * dpool[1][n][c] / ties[n][c]      accumulate != 0: in place on dx (rounded again) */
+size_t mcn_global_avgmax_pool_workspace_bytes(int32_t N, int64_t HW, int32_t C);
+int mcn_global_avgmax_pool_fwd(const void* x, void* pools, int32_t N, int64_t HW, int32_t C, mcn_dtype dtype, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int mcn_global_avgmax_pool_bwd(const void* dpool, const void* x, const void* pools, const float* ties, void* dx, int32_t accumulate, int32_t N,
+                               int64_t HW, int32_t C, mcn_dtype dtype, void* stream);
+int mcn_pair_sigmoid_fwd(const void* a, void* cm, int32_t N, int32_t C, mcn_dtype dtype, void* stream);
+int mcn_pair_sigmoid_bwd(const void* dcm, const void* cm, void* da, int32_t N, int32_t C, mcn_dtype dtype, void* stream);
+int mcn_cbam_chpool_fwd(const void* x, const void* cm, void* s, int32_t N, int64_t HW, int32_t C, mcn_dtype dtype, void* stream);
+int mcn_cbam_apply_fwd(const void* x, const void* cm, const void* s, const float* w, const float* b, void* sm, void* y, int32_t N, int32_t H,
+                       int32_t W, int32_t C, int32_t K, mcn_dtype dtype, void* stream);
+size_t mcn_cbam_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t K);
+int mcn_cbam_bwd(const void* dy, const void* x, const void* cm, const void* s, const void* sm, const float* w, const void* pools, void* dx,
+                 void* dcm, float* dw, float* db, float* ties, float grad_scale, int32_t N, int32_t H, int32_t W, int32_t C, int32_t K,
+                 mcn_dtype dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- element-wise -----------------------------------------------------------------------
  * tf.nn.relu / ReluGrad (convnet.py:2537); x + skip followed by relu (convnet.py:2511, 2537). */
 int mcn_relu_fwd(const void* x, void* y, int64_t n, mcn_dtype dtype, void* stream);

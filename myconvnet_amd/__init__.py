@@ -11,6 +11,7 @@ from .optimizers import MomentumOptimizer, Optimizer  # noqa: F401
 from .resnet_v1_5 import ResNet18, ResNet34, ResNet50, ResNet101  # noqa: F401
 from .resnet_v1_5_dilated import ResNet50OS8, ResNet50OS16, ResNet101OS8, ResNet101OS16, ResNetDilated  # noqa: F401
 from . import resnet_v1_5_wsgn  # noqa: F401  (the module: its ResNet50 ... carry the reference's names and would clash with the batch-norm family above)
+from .resnet_v2_d_cbam import ResNetCBAM, ResNetCBAM50, ResNetCBAM101  # noqa: F401
 from .segnet import SegNet  # noqa: F401
 from .vggnet import VGG16, VGG19  # noqa: F401
 

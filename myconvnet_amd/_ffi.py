@@ -160,6 +160,15 @@ SIGNATURES = {
     'mcn_gn_resident_ok': (c_int32, [c_int32, c_int32, c_int64, c_int32, c_int32, c_int]),
     'mcn_gn_fwd': (c_int, [c_void_p] * 7 + [c_int32, c_int64, c_int32, c_int32, c_float, c_int, c_int, c_int32, c_void_p, c_size_t, c_void_p]),
     'mcn_gn_bwd': (c_int, [c_void_p] * 10 + [c_float, c_int32, c_int64, c_int32, c_int32, c_int, c_int, c_int32, c_void_p, c_size_t, c_void_p]),
+    'mcn_global_avgmax_pool_workspace_bytes': (c_size_t, [c_int32, c_int64, c_int32]),
+    'mcn_global_avgmax_pool_fwd': (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int, c_void_p, c_size_t, c_void_p]),
+    'mcn_global_avgmax_pool_bwd': (c_int, [c_void_p] * 5 + [c_int32, c_int32, c_int64, c_int32, c_int, c_void_p]),
+    'mcn_pair_sigmoid_fwd': (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int, c_void_p]),
+    'mcn_pair_sigmoid_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int, c_void_p]),
+    'mcn_cbam_chpool_fwd': (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int, c_void_p]),
+    'mcn_cbam_apply_fwd': (c_int, [c_void_p] * 7 + [c_int32] * 5 + [c_int, c_void_p]),
+    'mcn_cbam_workspace_bytes': (c_size_t, [c_int32] * 5),
+    'mcn_cbam_bwd': (c_int, [c_void_p] * 12 + [c_float] + [c_int32] * 5 + [c_int, c_void_p, c_size_t, c_void_p]),
     'mcn_ws_table_bytes': (c_size_t, [ctypes.POINTER(WsJob), c_int32]),
     'mcn_ws_table_build': (c_int, [ctypes.POINTER(WsJob), c_int32, c_void_p, c_size_t, ctypes.POINTER(c_int32)]),
     'mcn_ws_fwd_workspace_bytes': (c_size_t, [ctypes.POINTER(WsJob), c_int32]),

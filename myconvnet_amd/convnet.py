@@ -823,6 +823,48 @@ class ConvNet(object):
         self.graph.node('chscale', [x, mask], [y], scope=self.scope_name())
         return y
 
+    def global_avgmax_pool(self, x):
+        """Stand-in for the pair tf.reduce_mean(x, axis=[1, 2]) / tf.reduce_max(x, axis=[1, 2]) at models/resnet_v2_d_cbam.py:176-177: ONE
+        [2N, C] tensor, the N mean rows first, then the N max rows (mcn_global_avgmax_pool_fwd: one read of x) — the rows the shared MLP of
+        _channel_mask (fc layers under reuse_variables(), :179-190) runs on once."""
+        n, h, w, c = x.shape
+        y = self.graph.tensor((2 * n, c), x.dtype, self.scope_name('avgmaxpool'))
+        self.graph.node('gavgmax', [x], [y], scope=self.scope_name())
+        return y
+
+    def pair_sigmoid(self, a):
+        """Stand-in for self.sigmoid(spatial_mean + spatial_max) + tf.reshape at models/resnet_v2_d_cbam.py:192-195 on the [2N, C] rows of
+        global_avgmax_pool's MLP: mask[n] = sigmoid(a[n] + a[N + n]), [N, C]."""
+        n2, c = a.shape
+        y = self.graph.tensor((n2 // 2, c), a.dtype, self.scope_name('sigmoid'))
+        self.graph.node('pairsig', [a], [y], scope=self.scope_name())
+        return y
+
+    def cbam_attention(self, x, channel_mask, kernel=7, scope='spatial_mask'):
+        """Stand-in for models/resnet_v2_d_cbam.py:161-165 + _spatial_mask (:199-211): (x * channel_mask) * spatial_mask, where spatial_mask =
+        sigmoid(conv_layer(concat(mean_c, max_c), kernel, 1, 1, SAME, biased)) of the product.  The product x * channel_mask is never stored:
+        'cbam_chpool' leaves the [N, H, W, 2] concat tensor, 'cbam_apply' the mask and the output (mcn_cbam_chpool_fwd / _apply_fwd /
+        mcn_cbam_bwd).  Variables as the reference names them: <scope>/conv/weights [k, k, 2, 1] and <scope>/conv/biases [1].
+        Returns (output, spatial_mask [N, H, W, 1])."""
+        n, h, w, c = x.shape
+        assert channel_mask.numel == n * c, 'channel mask {} for activations {}'.format(channel_mask.shape, x.shape)
+        assert kernel % 2 == 1 and kernel <= 7, 'the spatial-mask kernel must be odd and <= 7'
+        with self.variable_scope(scope):
+            with self.variable_scope('conv'):
+                wv = self.weight_variable([kernel, kernel, 2, 1])
+                bv = self.bias_variable(1)
+                cname = self.scope_name()
+            name = self.scope_name()
+        s = self.graph.tensor((n, h, w, 2), x.dtype, name + '/concat', self._channel_first)
+        sm = self.graph.tensor((n, h, w, 1), x.dtype, name + '/sigmoid', self._channel_first)
+        y = self.graph.tensor(x.shape, x.dtype, name + '/scale', self._channel_first)
+        self.graph.node('cbam_chpool', [x, channel_mask], [s], scope=name)
+        self.graph.node('cbam_apply', [x, channel_mask, s], [y, sm], scope=name, w=wv, b=bv, kernel=int(kernel), has_params=True)
+        flops = h * w * (kernel * kernel * 2 + 1)
+        self._conv_macs += h * w * kernel * kernel * 2
+        self._log_layer(cname, [None, h, w, 1], flops, kernel * kernel * 2 + 1, h * w)
+        return y, sm
+
     def _random_mask(self, x, kind, rate, name):
         """y = x * mask, mask drawn on the host each training step (sample_random_masks); identity in evaluation.
         kind 'sample': survived[n]/(1-rate) (stochastic depth); 'element': keep[n,c]/(1-rate) (dropout on [N,C])."""

@@ -806,6 +806,233 @@ extern "C" int mcn_gn_bwd(const void* dy, const void* x, const void* y, const fl
     });
 }
 
+// ---- CBAM attention tail (models/resnet_v2_d_cbam.py:159-211; mcn.h) -------------------------------------------------------------------------
+extern "C" size_t mcn_global_avgmax_pool_workspace_bytes(int32_t N, int64_t HW, int32_t C) { return (N > 0 && HW > 0 && C > 0) ? 256 : 0; }
+// [dt | per-pixel ties | ds (2 per pixel)]
+extern "C" size_t mcn_cbam_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t K) {
+    return (N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && K <= 7) ? (size_t)N * H * W * 4 * sizeof(float) + 256 : 0;
+}
+static int cbam_check(const char* who, int64_t N, int64_t H, int64_t W, int64_t C, int K, mcn_dtype dtype) {
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return fail(MCN_E_BADARG, "%s: bad argument", who);
+    if (K < 1 || K > 7 || !(K & 1)) return fail(MCN_E_BADARG, "%s: the kernel size must be odd and <= 7 (K=%d)", who, K);
+    if (dtype != MCN_F32 && dtype != MCN_BF16 && dtype != MCN_F16) return fail(MCN_E_UNSUPPORTED, "%s: dtype %d unsupported", who, (int)dtype);
+    if (C % (dtype == MCN_F32 ? 4 : 8)) return fail(MCN_E_UNSUPPORTED, "%s: C = %d is not a multiple of the 16-byte chunk", who, (int)C);
+    if (W > 512) return fail(MCN_E_UNSUPPORTED, "%s: W = %d (W <= 512)", who, (int)W);
+    return MCN_OK;
+}
+extern "C" int mcn_global_avgmax_pool_fwd(const void* x, void* pools, int32_t N, int64_t HW, int32_t C, mcn_dtype dtype, void* ws, size_t ws_bytes, void*) {
+    if (!x || !pools) return fail(MCN_E_BADARG, "global_avgmax_pool_fwd: null tensor");
+    if (int rc = cbam_check("global_avgmax_pool_fwd", N, HW, 1, C, 1, dtype)) return rc;
+    if (!ws || ws_bytes < mcn_global_avgmax_pool_workspace_bytes(N, HW, C)) return fail(MCN_E_WORKSPACE, "global_avgmax_pool_fwd: workspace too small");
+    return by_dtype(dtype, "global_avgmax_pool_fwd", [&](auto s) {
+        typedef decltype(s) S;
+        typedef typename S::T T;
+        const T* xp = (const T*)x;
+        T* o = (T*)pools;
+        const int64_t NC = (int64_t)N * C;
+#pragma omp parallel for schedule(static)
+        for (int64_t i = 0; i < NC; ++i) {
+            const int64_t n = i / C, c = i % C;
+            float a = 0.f, b = -INFINITY;
+            for (int64_t r = 0; r < HW; ++r) {
+                const float v = S::ld(xp + (n * HW + r) * C + c);
+                a += v;
+                b = std::max(b, v);
+            }
+            S::st(o + i, a / (float)HW);
+            S::st(o + NC + i, b);
+        }
+        return (int)MCN_OK;
+    });
+}
+extern "C" int mcn_global_avgmax_pool_bwd(const void* dpool, const void* x, const void* pools, const float* ties, void* dx, int32_t accumulate, int32_t N, int64_t HW,
+                                          int32_t C, mcn_dtype dtype, void*) {
+    if (!dpool || !x || !pools || !ties || !dx) return fail(MCN_E_BADARG, "global_avgmax_pool_bwd: null tensor");
+    if (int rc = cbam_check("global_avgmax_pool_bwd", N, HW, 1, C, 1, dtype)) return rc;
+    return by_dtype(dtype, "global_avgmax_pool_bwd", [&](auto s) {
+        typedef decltype(s) S;
+        typedef typename S::T T;
+        const T* dp = (const T*)dpool;
+        const T* xp = (const T*)x;
+        const T* pl = (const T*)pools;
+        T* o = (T*)dx;
+        const int64_t NC = (int64_t)N * C;
+#pragma omp parallel for schedule(static)
+        for (int64_t i = 0; i < NC; ++i) {
+            const int64_t n = i / C, c = i % C;
+            const float da = S::ld(dp + i) / (float)HW, dm = S::ld(dp + NC + i) / ties[i], pm = S::ld(pl + NC + i);
+            for (int64_t r = 0; r < HW; ++r) {
+                const int64_t q = (n * HW + r) * C + c;
+                S::st(o + q, (accumulate ? S::ld(o + q) : 0.f) + (da + (S::ld(xp + q) == pm ? dm : 0.f)));
+            }
+        }
+        return (int)MCN_OK;
+    });
+}
+extern "C" int mcn_pair_sigmoid_fwd(const void* a, void* cm, int32_t N, int32_t C, mcn_dtype dtype, void*) {
+    if (!a || !cm) return fail(MCN_E_BADARG, "pair_sigmoid_fwd: null tensor");
+    if (N <= 0 || C <= 0) return fail(MCN_E_BADARG, "pair_sigmoid_fwd: bad argument");
+    return by_dtype(dtype, "pair_sigmoid_fwd", [&](auto s) {
+        typedef decltype(s) S;
+        typedef typename S::T T;
+        const int64_t NC = (int64_t)N * C;
+        for (int64_t i = 0; i < NC; ++i) S::st((T*)cm + i, sigmoidf(S::ld((const T*)a + i) + S::ld((const T*)a + NC + i)));
+        return (int)MCN_OK;
+    });
+}
+extern "C" int mcn_pair_sigmoid_bwd(const void* dcm, const void* cm, void* da, int32_t N, int32_t C, mcn_dtype dtype, void*) {
+    if (!dcm || !cm || !da) return fail(MCN_E_BADARG, "pair_sigmoid_bwd: null tensor");
+    if (N <= 0 || C <= 0) return fail(MCN_E_BADARG, "pair_sigmoid_bwd: bad argument");
+    return by_dtype(dtype, "pair_sigmoid_bwd", [&](auto s) {
+        typedef decltype(s) S;
+        typedef typename S::T T;
+        const int64_t NC = (int64_t)N * C;
+        for (int64_t i = 0; i < NC; ++i) {
+            const float m = S::ld((const T*)cm + i), d = S::ld((const T*)dcm + i) * m * (1.f - m);
+            S::st((T*)da + i, d);
+            S::st((T*)da + NC + i, d);
+        }
+        return (int)MCN_OK;
+    });
+}
+extern "C" int mcn_cbam_chpool_fwd(const void* x, const void* cm, void* so, int32_t N, int64_t HW, int32_t C, mcn_dtype dtype, void*) {
+    if (!x || !cm || !so) return fail(MCN_E_BADARG, "cbam_chpool_fwd: null tensor");
+    if (int rc = cbam_check("cbam_chpool_fwd", N, HW, 1, C, 1, dtype)) return rc;
+    return by_dtype(dtype, "cbam_chpool_fwd", [&](auto s) {
+        typedef decltype(s) S;
+        typedef typename S::T T;
+        const T* xp = (const T*)x;
+        const T* mp = (const T*)cm;
+        T* o = (T*)so;
+#pragma omp parallel for schedule(static)
+        for (int64_t q = 0; q < (int64_t)N * HW; ++q) {
+            const int64_t n = q / HW;
+            float a = 0.f, b = -INFINITY;
+            for (int c = 0; c < C; ++c) {
+                const float v = rnd<S>(S::ld(xp + q * C + c) * S::ld(mp + n * C + c));
+                a += v;
+                b = std::max(b, v);
+            }
+            S::st(o + q * 2, a / (float)C);
+            S::st(o + q * 2 + 1, b);
+        }
+        return (int)MCN_OK;
+    });
+}
+extern "C" int mcn_cbam_apply_fwd(const void* x, const void* cm, const void* sv, const float* w, const float* b, void* sm, void* y, int32_t N, int32_t H, int32_t W,
+                                  int32_t C, int32_t K, mcn_dtype dtype, void*) {
+    if (!x || !cm || !sv || !w || !sm || !y) return fail(MCN_E_BADARG, "cbam_apply_fwd: null tensor");
+    if (int rc = cbam_check("cbam_apply_fwd", N, H, W, C, K, dtype)) return rc;
+    return by_dtype(dtype, "cbam_apply_fwd", [&](auto s) {
+        typedef decltype(s) S;
+        typedef typename S::T T;
+        const T* xp = (const T*)x;
+        const T* mp = (const T*)cm;
+        const T* sp = (const T*)sv;
+        T* smo = (T*)sm;
+        T* yo = (T*)y;
+        const std::vector<float> wq = cast_weights<S>(w, (size_t)2 * K * K);
+        const int P = K / 2;
+#pragma omp parallel for schedule(static)
+        for (int64_t q = 0; q < (int64_t)N * H * W; ++q) {
+            const int64_t n = q / ((int64_t)H * W);
+            const int py = (int)(q / W % H), px = (int)(q % W);
+            float acc = b ? b[0] : 0.f;
+            for (int a = 0; a < K; ++a)
+                for (int c = 0; c < K; ++c) {
+                    const int gy = py + a - P, gx = px + c - P;
+                    if (gy < 0 || gy >= H || gx < 0 || gx >= W) continue;
+                    const T* t = sp + ((n * H + gy) * W + gx) * 2;
+                    acc += S::ld(t) * wq[(a * K + c) * 2] + S::ld(t + 1) * wq[(a * K + c) * 2 + 1];
+                }
+            const float sg = rnd<S>(sigmoidf(rnd<S>(acc)));
+            S::st(smo + q, sg);
+            for (int c = 0; c < C; ++c) S::st(yo + q * C + c, rnd<S>(S::ld(xp + q * C + c) * S::ld(mp + n * C + c)) * sg);
+        }
+        return (int)MCN_OK;
+    });
+}
+extern "C" int mcn_cbam_bwd(const void* dy, const void* x, const void* cm, const void* sv, const void* sm, const float* w, const void* pools, void* dx, void* dcm, float* dw,
+                            float* db, float* ties, float grad_scale, int32_t N, int32_t H, int32_t W, int32_t C, int32_t K, mcn_dtype dtype, void* ws, size_t ws_bytes, void*) {
+    if (!dy || !x || !cm || !sv || !sm || !w || !dx || !dcm) return fail(MCN_E_BADARG, "cbam_bwd: null tensor");
+    if ((pools != nullptr) != (ties != nullptr)) return fail(MCN_E_BADARG, "cbam_bwd: pools and ties go together");
+    if (int rc = cbam_check("cbam_bwd", N, H, W, C, K, dtype)) return rc;
+    if (!ws || ws_bytes < mcn_cbam_workspace_bytes(N, H, W, C, K)) return fail(MCN_E_WORKSPACE, "cbam_bwd: workspace too small");
+    return by_dtype(dtype, "cbam_bwd", [&](auto s) {
+        typedef decltype(s) S;
+        typedef typename S::T T;
+        const T* gp = (const T*)dy;
+        const T* xp = (const T*)x;
+        const T* mp = (const T*)cm;
+        const T* sp = (const T*)sv;
+        const T* smp = (const T*)sm;
+        const int64_t HW = (int64_t)H * W, NP = (int64_t)N * HW, NC = (int64_t)N * C;
+        const T* pm = pools ? (const T*)pools + NC : nullptr;
+        float* dt = (float*)ws;
+        float* tp = dt + NP;
+        float* ds = tp + NP;
+        const std::vector<float> wq = cast_weights<S>(w, (size_t)2 * K * K);
+        const int P = K / 2;
+#pragma omp parallel for schedule(static)
+        for (int64_t q = 0; q < NP; ++q) {
+            const int64_t n = q / HW;
+            const float smax = S::ld(sp + q * 2 + 1), sg = S::ld(smp + q);
+            float a = 0.f, t = 0.f;
+            for (int c = 0; c < C; ++c) {
+                const float v = rnd<S>(S::ld(xp + q * C + c) * S::ld(mp + n * C + c));
+                a += S::ld(gp + q * C + c) * v;
+                t += v == smax ? 1.f : 0.f;
+            }
+            dt[q] = a * sg * (1.f - sg);
+            tp[q] = t;
+        }
+        std::vector<double> dwa((size_t)2 * K * K + 1, 0.0);
+        for (int64_t q = 0; q < NP; ++q) {
+            const int64_t n = q / HW;
+            const int py = (int)(q / W % H), px = (int)(q % W);
+            float d0 = 0.f, d1 = 0.f;
+            for (int a = 0; a < K; ++a)
+                for (int c = 0; c < K; ++c) {
+                    const int gy = py + a - P, gx = px + c - P;             // forward tap (a, c) of pixel q reads s here ...
+                    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+                        const T* t = sp + ((n * H + gy) * W + gx) * 2;
+                        dwa[(a * K + c) * 2] += (double)dt[q] * S::ld(t);
+                        dwa[(a * K + c) * 2 + 1] += (double)dt[q] * S::ld(t + 1);
+                    }
+                    const int hy = py - (a - P), hx = px - (c - P);         // ... and pixel (hy, hx) reads s[q] through it
+                    if (hy >= 0 && hy < H && hx >= 0 && hx < W) {
+                        const float d = dt[(n * H + hy) * W + hx];
+                        d0 += d * wq[(a * K + c) * 2];
+                        d1 += d * wq[(a * K + c) * 2 + 1];
+                    }
+                }
+            dwa[(size_t)2 * K * K] += dt[q];
+            ds[q * 2] = d0;
+            ds[q * 2 + 1] = d1;
+        }
+        for (int t = 0; t < 2 * K * K; ++t)
+            if (dw) dw[t] = (float)dwa[t] * grad_scale;
+        if (db) db[0] = (float)dwa[(size_t)2 * K * K] * grad_scale;
+#pragma omp parallel for schedule(static)
+        for (int64_t i = 0; i < NC; ++i) {
+            const int64_t n = i / C, c = i % C;
+            const float m = S::ld(mp + i), pmax = pm ? S::ld(pm + i) : NAN;
+            float a = 0.f, t = 0.f;
+            for (int64_t r = 0; r < HW; ++r) {
+                const int64_t q = n * HW + r;
+                const float xv = S::ld(xp + q * C + c), v = rnd<S>(xv * m);
+                const float d = S::ld(gp + q * C + c) * S::ld(smp + q) + ds[q * 2] / (float)C + (v == S::ld(sp + q * 2 + 1) ? ds[q * 2 + 1] / tp[q] : 0.f);
+                a += d * xv;
+                t += xv == pmax ? 1.f : 0.f;
+                S::st((T*)dx + q * C + c, d * m);
+            }
+            S::st((T*)dcm + i, a);
+            if (ties) ties[i] = t;
+        }
+        return (int)MCN_OK;
+    });
+}
+
 // ---- element-wise ------------------------------------------------------------------------------------------------------------------------
 template <typename S, typename F>
 static int map_n(int64_t n, F&& f) {

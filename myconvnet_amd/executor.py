@@ -109,6 +109,11 @@ class Lowering(object):
             elif n.op == 'fc':
                 x = n.inputs[0]
                 need = max(need, lib.mcn_fc_workspace_bytes(x.shape[0], x.shape[1], n.outputs[0].shape[1], self.dt))
+            elif n.op == 'gavgmax':
+                N, H, W, C = n.inputs[0].shape
+                need = max(need, lib.mcn_global_avgmax_pool_workspace_bytes(N, H * W, C))
+            elif n.op == 'cbam_apply':
+                need = max(need, lib.mcn_cbam_workspace_bytes(*self._cbam_dims(n)))
             elif n.op == 'biasadd':
                 x = n.inputs[0]
                 need = max(need, lib.mcn_bias_grad_workspace_bytes(x.numel // x.shape[-1], x.shape[-1]))
@@ -983,6 +988,77 @@ class Lowering(object):
         if post:
             self.bwd.add(lib.mcn_accumulate, *post)
         self.bwd.mark(('grad_ready', tuple(v.name for v in (g, b) if v is not None and v.trainable)))
+
+    # ---- CBAM attention tail (models/resnet_v2_d_cbam.py:159-211) ---------------------------------------------------------------
+    def _cbam_dims(self, n):
+        """(N, H, W, C, K) of a 'cbam_apply' node"""
+        x = n.inputs[0]
+        assert x.cs == x.shape[-1], 'the attention tail needs a dense channel axis'
+        return tuple(x.shape) + (n.attrs['kernel'],)
+
+    def fwd_gavgmax(self, n):
+        x, y = n.inputs[0], n.outputs[0]
+        N, H, W, C = x.shape
+        self.fwd.add(lib.mcn_global_avgmax_pool_fwd, x.buf.data_ptr(), y.buf.data_ptr(), N, H * W, C, MCN_DT[x.dtype], self.ws_ptr, self.ws_bytes)
+
+    def bwd_gavgmax(self, n):
+        """Runs behind the MLP's backward: adds the pool gradient to x.grad in place.  The tie counts of the spatial maxima come from the pass
+        over x that mcn_cbam_bwd makes anyway (bwd_cbam_apply, earlier in the backward list)."""
+        x, y = n.inputs[0], n.outputs[0]
+        N, H, W, C = x.shape
+        if 'ties' not in n.attrs:
+            raise NotImplementedError('global_avgmax_pool: the backward takes its tie counts from cbam_attention on the same tensor')
+        self.contribute(x, lambda dst, acc: self.bwd.add(lib.mcn_global_avgmax_pool_bwd, y.grad.data_ptr(), x.buf.data_ptr(), y.buf.data_ptr(), n.attrs['ties'].data_ptr(),
+                                                         dst, acc, N, H * W, C, MCN_DT[x.dtype]))
+
+    def fwd_pairsig(self, n):
+        a, y = n.inputs[0], n.outputs[0]
+        self.fwd.add(lib.mcn_pair_sigmoid_fwd, a.buf.data_ptr(), y.buf.data_ptr(), y.shape[0], y.shape[1], MCN_DT[a.dtype])
+
+    def bwd_pairsig(self, n):
+        a, y = n.inputs[0], n.outputs[0]
+        self.contribute_via_scratch(a, lambda dst: self.bwd.add(lib.mcn_pair_sigmoid_bwd, y.grad.data_ptr(), y.buf.data_ptr(), dst, y.shape[0], y.shape[1], MCN_DT[a.dtype]))
+
+    def fwd_cbam_chpool(self, n):
+        x, cm, s = n.inputs[0], n.inputs[1], n.outputs[0]
+        N, H, W, C = x.shape
+        self.fwd.add(lib.mcn_cbam_chpool_fwd, x.buf.data_ptr(), cm.buf.data_ptr(), s.buf.data_ptr(), N, H * W, C, MCN_DT[x.dtype])
+
+    def fwd_cbam_apply(self, n):
+        """inference reads the EMA shadows of the 7x7 filter and its bias (vptr), as every layer does"""
+        x, cm, s = n.inputs
+        y, sm = n.outputs
+        self.fwd.add(lib.mcn_cbam_apply_fwd, x.buf.data_ptr(), cm.buf.data_ptr(), s.buf.data_ptr(), self.vptr(n.attrs['w']), self.vptr(n.attrs['b']), sm.buf.data_ptr(),
+                     y.buf.data_ptr(), *(self._cbam_dims(n) + (MCN_DT[x.dtype],)))
+
+    def bwd_cbam_apply(self, n):
+        """One call for 'cbam_chpool' + 'cbam_apply' (the former has no backward of its own): x and cm are the saved inputs, the product is
+        recomputed.  The spatial mask is an output for inspection only: a gradient arriving on it is not part of the built path."""
+        x, cm, s = n.inputs
+        y, sm = n.outputs
+        w, b = n.attrs['w'], n.attrs['b']
+        post = []
+
+        def target(t, key):
+            if t.needs_grad and t.id not in self.written:
+                self.written.add(t.id)
+                return t.grad.data_ptr()
+            sc = self.scratch_like(t, key)
+            if t.needs_grad:
+                post.append((t.grad.data_ptr(), sc.data_ptr(), t.grad.numel(), MCN_DT[t.dtype]))
+            return sc.data_ptr()
+        pools = ties = 0
+        gav = [c for c in x.consumers if c.op == 'gavgmax' and c in self.g.nodes]
+        if gav and gav[0].outputs[0].needs_grad:
+            gav[0].attrs['ties'] = torch.zeros((x.shape[0], x.shape[-1]), dtype=torch.float32, device=self.g.device)
+            pools, ties = gav[0].outputs[0].buf.data_ptr(), gav[0].attrs['ties'].data_ptr()
+        dx, dcm = target(x, 'cbam_dx'), target(cm, 'cbam_dcm')
+        self.bwd.add(lib.mcn_cbam_bwd, y.grad.data_ptr(), x.buf.data_ptr(), cm.buf.data_ptr(), s.buf.data_ptr(), sm.buf.data_ptr(), w.data.data_ptr(), pools, dx, dcm,
+                     w.grad.data_ptr() if w.trainable else 0, b.grad.data_ptr() if b.trainable else 0, ties, 1.0 / self.loss_scale,
+                     *(self._cbam_dims(n) + (MCN_DT[x.dtype], self.ws_ptr, self.ws_bytes)))
+        for a in post:
+            self.bwd.add(lib.mcn_accumulate, *a)
+        self.bwd.mark(('grad_ready', tuple(v.name for v in (w, b) if v.trainable)))
 
     # ---- element-wise ----------------------------------------------------------------------------------------------
     def fwd_affine(self, n):
