@@ -164,6 +164,42 @@ int mcn_conv2d_wgrad(const void* x, const void* dy, float* dw_hwio, float* dbias
                      float grad_scale, mcn_dtype dtype, mcn_layout layout, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ---- transposed convolution ---------------------------------------------------------------
+ * replaces tf.nn.conv2d_transpose [+ tf.nn.bias_add] (reference convnet.py:2463, 2486).  x:[N][h][w][Cs] (the small input),
+ * w: fp32 master [KH][KW][Cs][Cb] (the reference's variable, convnet.py:2460), y:[N][OH][OW][Cb]:
+ *   y[n,oy,ox,cb] = bias[cb] + sum over (r,q) with (oy+padT-r) % SH == 0, (ox+padL-q) % SW == 0 and the quotients inside [0,h) x [0,w)
+ *                   of sum_cs x[n,(oy+padT-r)/SH,(ox+padL-q)/SW,cs] * round(w[r][q][cs][cb])
+ * `g` describes the strided convolution that maps y's grid back to x's: H, W = OH, OW; Cin = Cb; Cout = Cs; the pads of that convolution
+ * (TF SAME on the big grid: total = max((ceil(OH/SH)-1)*SH + KH - OH, 0), before = total/2; VALID: 0); h, w follow as that convolution's
+ * output size.  With pads, OH outside (h-1)*SH+1 .. h*SH (OW likewise) is MCN_E_BADARG, as are NULL tensors; dilation != 1 is
+ * MCN_E_UNSUPPORTED; a short workspace MCN_E_WORKSPACE.  SH, SW <= 2, KH, KW <= 7 and Cs a multiple of the 16-byte chunk run the
+ * phase-fused MFMA kernel (csrc/deconv.hip: every stride phase from one staged input window, one launch) when Cb <= 16, when g->tile == 1
+ * (g->tile == 2 forces the other route: for callers that time both),
+ * or when the layer is biased and light (KH*KW*Cs / (SH*SW) <= 400 MACs per output element); other geometries of that range run
+ * mcn_filter_swap_io + mcn_conv2d_dgrad + a bias pass, all three timed together against the fused kernel (DESIGN.md section 3;
+ * mcn_deconv2d_kernel_name answers for a biased layer); everything else a gather kernel.  No atomics: a repeated call is bit-identical.
+ * w_packed (may be NULL): mcn_deconv2d_pack's operand (mcn_deconv2d_packed_bytes() bytes; 0: this geometry takes none) — all taps
+ * K-contiguous in the order the kernel walks them; when NULL the call re-packs w into `workspace` itself.
+ * workspace: mcn_deconv2d_workspace_bytes(op, g, dtype), op = MCN_CONV_FWD / _DGRAD / _WGRAD for the three calls.
+ * mcn_deconv2d_dgrad: dx[N][h][w][Cs] = mcn_conv2d_fwd(dy) on `g` with the filter [KH][KW][Cb][Cs].  w_swapped (may be NULL: swapped from w
+ *   into the workspace per call) = mcn_filter_swap_io(w, ., KH*KW, Cs, Cb, 1); w_swapped_packed (may be NULL) = the MCN_CONV_FWD pack job of
+ *   `g` reading w_swapped.
+ * mcn_deconv2d_wgrad: dw[KH][KW][Cs][Cb] = grad_scale * swap(mcn_conv2d_wgrad(x := dy, dy := x)) (deterministic as that call is),
+ *   dbias (optional) = grad_scale * column sums of dy (mcn_bias_grad).
+ * mcn_filter_swap_io: fp32 dst[t][b][a] = scale * src[t][a][b] (tile transpose through LDS; src != dst).
+ * mcn_deconv2d_kernel_name: profiling aid as mcn_conv2d_kernel_name (buf >= 64 bytes; returns the number of launches). */
+size_t mcn_deconv2d_workspace_bytes(mcn_conv_op op, const mcn_conv_geom* g, mcn_dtype dtype);
+size_t mcn_deconv2d_packed_bytes(const mcn_conv_geom* g, mcn_dtype dtype);
+int mcn_deconv2d_pack(const float* w, void* packed, const mcn_conv_geom* g, mcn_dtype dtype, void* stream);
+int mcn_deconv2d_kernel_name(const mcn_conv_geom* g, mcn_dtype dtype, char* buf, size_t buflen);
+int mcn_deconv2d_fwd(const void* x, const float* w, const void* w_packed, const float* bias, void* y, const mcn_conv_geom* g, mcn_dtype dtype,
+                     mcn_layout layout, void* workspace, size_t workspace_bytes, void* stream);
+int mcn_deconv2d_dgrad(const void* dy, const float* w, const float* w_swapped, const void* w_swapped_packed, void* dx, const mcn_conv_geom* g,
+                       mcn_dtype dtype, mcn_layout layout, void* workspace, size_t workspace_bytes, void* stream);
+int mcn_deconv2d_wgrad(const void* x, const void* dy, float* dw, float* dbias, const mcn_conv_geom* g, float grad_scale, mcn_dtype dtype,
+                       mcn_layout layout, void* workspace, size_t workspace_bytes, void* stream);
+int mcn_filter_swap_io(const float* src, float* dst, int32_t taps, int32_t A, int32_t B, float scale, void* stream);
+
 /* ---- batch normalisation ----------------------------------------------------------------
  * x,y:[M][C] (M = N*H*W).  replaces tf.nn.fused_batch_norm(is_training=True) and the running
  * statistics update (reference convnet.py:1883-1888, 1898-1914):

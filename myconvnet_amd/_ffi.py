@@ -73,6 +73,14 @@ SIGNATURES = {
     'mcn_conv2d_kernel_name': (c_int, [c_int, ctypes.POINTER(ConvGeom), c_int, ctypes.c_char_p, c_size_t]),
     'mcn_conv2d_launch_list': (c_int, [c_int, ctypes.POINTER(ConvGeom), c_int, ctypes.c_char_p, c_size_t]),
     'mcn_conv2d_wgrad': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(ConvGeom), c_float, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'mcn_deconv2d_workspace_bytes': (c_size_t, [c_int, ctypes.POINTER(ConvGeom), c_int]),
+    'mcn_deconv2d_packed_bytes': (c_size_t, [ctypes.POINTER(ConvGeom), c_int]),
+    'mcn_deconv2d_pack': (c_int, [c_void_p, c_void_p, ctypes.POINTER(ConvGeom), c_int, c_void_p]),
+    'mcn_deconv2d_kernel_name': (c_int, [ctypes.POINTER(ConvGeom), c_int, ctypes.c_char_p, c_size_t]),
+    'mcn_deconv2d_fwd': (c_int, [c_void_p] * 5 + [ctypes.POINTER(ConvGeom), c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'mcn_deconv2d_dgrad': (c_int, [c_void_p] * 5 + [ctypes.POINTER(ConvGeom), c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'mcn_deconv2d_wgrad': (c_int, [c_void_p] * 4 + [ctypes.POINTER(ConvGeom), c_float, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'mcn_filter_swap_io': (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p]),
     'mcn_bn_workspace_bytes': (c_size_t, [c_int64, c_int32]),
     'mcn_bn_relu_mask_bytes': (c_size_t, [c_int64, c_int32, c_int]),
     'mcn_bn_fwd_train': (c_int, [c_void_p] * 12 + [c_float, c_int64, c_int32, c_float, c_int, c_int, c_void_p, c_size_t, c_void_p]),

@@ -12,7 +12,10 @@ executor standardises every such filter in one batched launch pair per step and 
 
 Not built (raise NotImplementedError): weight standardisation of depthwise filters and of fc_layer, the normalization()
 dispatcher for anything but 'batch' (group_norm itself is built: a model calls it from _build_model),
-augmentation, dropout rate > 0, transposed conv / upsampling (SURVEY.md §8f "next" rows).
+augmentation, dropout rate > 0 (SURVEY.md §8f "next" rows).
+
+Transposed convolution (transposed_conv_layer, reference convnet.py:2408-2498) is built for dilation 1, NHWC, without weight standardisation:
+one 'deconv' node, forward in csrc/deconv.hip, backward on the strided convolution's kernels.
 """
 import math
 import os
@@ -593,6 +596,51 @@ class ConvNet(object):
         flops = oh * ow * kernel[0] * kernel[1] * cin * out_channels
         params = kernel[0] * kernel[1] * cin * out_channels
         self._conv_macs += flops
+        if biased:
+            flops += oh * ow * out_channels
+            params += out_channels
+        self._log_layer(name, [None, oh, ow, out_channels], flops, params, oh * ow * out_channels)
+        return y
+
+    def transposed_conv_layer(self, x, kernel, stride, out_channels, padding='SAME', biased=True, output_shape=None,
+                              dilation=(1, 1), scope=None, weight_initializer=None, bias_initializer=None, ws=False,
+                              verbose=False):
+        """reference convnet.py:2408-2498 -> tf.nn.conv2d_transpose (:2463) [+ tf.nn.bias_add (:2486)]: one 'deconv' node
+        (mcn_deconv2d_fwd / _dgrad / _wgrad).  Variables: weights [kh, kw, in, out] and biases under the caller's scope.  The output size must
+        be one that the strided convolution of the same padding maps back to the input size (TensorFlow raises otherwise); SAME defaults to
+        h * stride.  output_shape: [n, oh, ow, c] as the reference passes it, or (oh, ow)."""
+        kernel, stride, dilation = _pair(kernel), _pair(stride), _pair(dilation)
+        if tuple(dilation) != (1, 1):
+            raise NotImplementedError('transposed_conv_layer: dilation {} is not built'.format(tuple(dilation)))
+        if ws:
+            raise NotImplementedError('transposed_conv_layer: weight standardisation is not built')
+        if self._channel_first:
+            raise NotImplementedError('transposed_conv_layer: channel_first is not built')
+        n, h, w, cin = x.shape
+        same = padding.upper() == 'SAME'
+        if output_shape is None:
+            size = [h * stride[0], w * stride[1]] if same else [h * stride[0] - kernel[0] + 1, w * stride[1] - kernel[1] + 1]
+        else:
+            size = [int(v) for v in (output_shape[1:3] if len(output_shape) == 4 else output_shape)]
+        pads = []
+        for o, i, k, s in zip(size, (h, w), kernel, stride):
+            pads += list(same_pads(o, k, s, 1)) if (same and o > 0) else [0, 0]
+            if o <= 0 or out_size(o, k, s, padding, 1) != i:
+                raise ValueError('transposed_conv_layer: a {} convolution (kernel {}, stride {}) does not map an output size of {} back to the input size {}'
+                                 .format(padding.upper(), k, s, o, i))
+        oh, ow = size
+        with self.variable_scope(scope) if scope is not None else nullcontext():
+            wv = self.weight_variable([kernel[0], kernel[1], cin, out_channels], initializer=weight_initializer)
+            bv = self.bias_variable(out_channels, initializer=bias_initializer) if biased else None
+            name = self.scope_name()
+        y = self.graph.tensor((n, oh, ow, out_channels), x.dtype, name + '/conv2d_transpose', self._channel_first)
+        # the strided convolution that maps y's grid back to x's (include/mcn.h): H, W = output size, Cin = out, Cout = in
+        geom = _ffi.conv_geom(n, oh, ow, out_channels, cin, kernel[0], kernel[1], stride[0], stride[1], 1, 1, tuple(pads), 0)
+        assert x.cs == cin, 'transposed_conv_layer needs a dense channel axis'
+        self.graph.node('deconv', [x], [y], scope=name, geom=geom, w=wv, b=bv, has_params=True)
+        flops = oh * ow * kernel[0] * kernel[1] * cin * out_channels
+        params = kernel[0] * kernel[1] * cin * out_channels
+        self._conv_macs += h * w * kernel[0] * kernel[1] * cin * out_channels
         if biased:
             flops += oh * ow * out_channels
             params += out_channels

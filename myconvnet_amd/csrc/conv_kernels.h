@@ -21,9 +21,8 @@
 #pragma once
 #include <type_traits>
 #include "common.h"
+#include "mma_nt.h"
 
-#define MCN_MAX_TAPS 64
-#define MCN_OOB 0x80000000u
 // Timing probes inside the kernels (MCN_NT_EPI_FLAGS / MCN_TN_DBG: skip a kind of instruction, wrong results) are compiled in only with
 // -DMCN_KERNEL_PROBES=1: as run-time branches they split the K loop into basic blocks the scheduler does not interleave across
 // (measured on conv_gemm_nt_wpp: 49 us without, 60 us with four such branches in the loop, profiles/round4_nt_wpp_probe_bf16.txt).
@@ -72,15 +71,6 @@ struct GemmNTParams {
                             // (byte tables are fetched with vector loads whose waits drain the LDS-DMA queue)
 };
 
-// Cache policy of the LDS-DMA loads of the activation operands (build-time experiments): the aux immediate of buffer_load ... lds,
-// 2 = nt (streaming).  MCN_DMA_AUX_A: A operand of the NT kernels (activations; the packed filter stays cached); MCN_DMA_AUX_X: x and dy
-// of the wgrad.
-#ifndef MCN_DMA_AUX_A
-#define MCN_DMA_AUX_A 0
-#endif
-#ifndef MCN_DMA_AUX_X
-#define MCN_DMA_AUX_X 0
-#endif
 struct GemmTNParams {
     const void* x;
     const void* dy;
@@ -111,58 +101,6 @@ __device__ __forceinline__ i32x4 buf_load16_epi(__amdgpu_buffer_rsrc_t rs, unsig
     return __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, MCN_EPI_AUX);
 }
 
-// ------------------------------------------------------------------------------------------------
-// MFMA policies
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-struct MmaNT;
-
-// bf16: 16x16x32, K-step = 64 elements = 2 slabs; fragment = one 16-byte chunk
-template <>
-struct MmaNT<bf16_t> {
-    static constexpr int MT = 16;       // tile edge
-    static constexpr int SLABS = 2;     // per 128-byte K-step
-    static constexpr int CPS = 4;       // chunks per slab
-    typedef f32x4 Acc;
-    typedef bf16x8 Frag;
-    static __device__ __forceinline__ int frag_row(int lane) { return lane & 15; }
-    static __device__ __forceinline__ int frag_chunk(int lane) { return lane >> 4; }
-    static __device__ __forceinline__ void mma(Acc& acc, const Frag& w, const Frag& x) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, acc, 0, 0, 0);
-    }
-};
-// fp16: the bf16 policy with the f16 MFMA (same cycles, same operand / accumulator lane maps)
-template <>
-struct MmaNT<f16_t> {
-    static constexpr int MT = 16;
-    static constexpr int SLABS = 2;
-    static constexpr int CPS = 4;
-    typedef f32x4 Acc;
-    typedef f16x8 Frag;
-    static __device__ __forceinline__ int frag_row(int lane) { return lane & 15; }
-    static __device__ __forceinline__ int frag_chunk(int lane) { return lane >> 4; }
-    static __device__ __forceinline__ void mma(Acc& acc, const Frag& w, const Frag& x) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, x, acc, 0, 0, 0);
-    }
-};
-// fp32: 32x32x2; a 16-byte fragment (4 consecutive k) feeds 4 MFMAs (k pairs {e, 4+e})
-template <>
-struct MmaNT<float> {
-    static constexpr int MT = 32;
-    static constexpr int SLABS = 4;
-    static constexpr int CPS = 2;
-    typedef f32x16 Acc;
-    typedef f32x4 Frag;
-    static __device__ __forceinline__ int frag_row(int lane) { return lane & 31; }
-    static __device__ __forceinline__ int frag_chunk(int lane) { return lane >> 5; }
-    static __device__ __forceinline__ void mma(Acc& acc, const Frag& w, const Frag& x) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[e], x[e], acc, 0, 0, 0);
-    }
-};
-
-// LDS image of an NT tile: rows of 128 bytes, 16-byte chunk c of row r at r*128 + ((c ^ ((r>>1)&7))<<4)
-__device__ __forceinline__ int nt_lds_off(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
 
 // Halving butterfly over lanes (see the statistics epilogue of conv_gemm_nt): C values left, partner offset O.  All array
 // indices are compile-time constants (a run-time count makes the compiler index the register arrays with select chains).
@@ -245,13 +183,6 @@ enum { NT_LINEAR = 0, NT_UNIFORM = 1, NT_GENERIC = 2 };
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (N > 0) {
-        static_for<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
 
 // Epilogue of conv_gemm_nt / conv_nt_sk_reduce: bias, store (or accumulate), optional BN-statistics partials.
 // EPI: 0 = store, 1 = store + BN-statistics partials, 2 = accumulate (p.accumulate 1 / 2) — compile-time so that the plain

@@ -1720,3 +1720,102 @@ extern "C" int mcn_bn_running_chain_strided(float* running, const float* batch, 
 extern "C" int mcn_bn_running_chain(float* running, const float* batch, int32_t towers, int64_t n, float momentum, void* s) {
     return mcn_bn_running_chain_strided(running, batch, towers, n, n, momentum, s);
 }
+
+// ---- transposed convolution (csrc/deconv.hip) -------------------------------------------------------------------------------------------------------
+// The gather formula of include/mcn.h as loops; the backward is the strided convolution of the same geometry (mcn_conv2d_fwd / _wgrad above) on the
+// filter with its channel axes swapped.
+struct DGeo { int N, h, w, Cs, Cb, OH, OW, KH, KW, SH, SW, pT, pL; };
+static int dgeo_from(const mcn_conv_geom* g, mcn_dtype dtype, DGeo* o) {
+    if (!g) return fail(MCN_E_BADARG, "deconv: null geometry");
+    if (dtype != MCN_F32 && dtype != MCN_BF16 && dtype != MCN_F16) return fail(MCN_E_UNSUPPORTED, "deconv: dtype %d", (int)dtype);
+    if (g->N < 0 || g->H <= 0 || g->W <= 0 || g->Cin <= 0 || g->Cout <= 0 || g->KH <= 0 || g->KW <= 0 || g->SH <= 0 || g->SW <= 0 || g->padT < 0 || g->padB < 0 ||
+        g->padL < 0 || g->padR < 0 || (g->x_cs != 0 && g->x_cs != g->Cin) || g->KH * g->KW > 64)
+        return fail(MCN_E_BADARG, "deconv: bad geometry");
+    if (g->DH != 1 || g->DW != 1) return fail(MCN_E_UNSUPPORTED, "deconv: dilation %dx%d is not built", g->DH, g->DW);
+    if (g->H + g->padT + g->padB < g->KH || g->W + g->padL + g->padR < g->KW) return fail(MCN_E_BADARG, "deconv: output smaller than the filter");
+    *o = DGeo{g->N, (g->H + g->padT + g->padB - g->KH) / g->SH + 1, (g->W + g->padL + g->padR - g->KW) / g->SW + 1, g->Cout, g->Cin, g->H, g->W, g->KH, g->KW,
+              g->SH, g->SW, g->padT, g->padL};
+    if ((g->padT || g->padB) && (g->H < (o->h - 1) * g->SH + 1 || g->H > o->h * g->SH)) return fail(MCN_E_BADARG, "deconv: output height %d does not map to %d", g->H, o->h);
+    if ((g->padL || g->padR) && (g->W < (o->w - 1) * g->SW + 1 || g->W > o->w * g->SW)) return fail(MCN_E_BADARG, "deconv: output width %d does not map to %d", g->W, o->w);
+    return MCN_OK;
+}
+static size_t dc_swap_bytes(const DGeo& d) { return ((size_t)d.KH * d.KW * d.Cs * d.Cb * sizeof(float) + 255) / 256 * 256; }
+extern "C" size_t mcn_deconv2d_packed_bytes(const mcn_conv_geom*, mcn_dtype) { return 0; }
+extern "C" int mcn_deconv2d_pack(const float*, void*, const mcn_conv_geom*, mcn_dtype, void*) { UNSUPPORTED("deconv2d_pack"); }
+extern "C" int mcn_deconv2d_kernel_name(const mcn_conv_geom*, mcn_dtype, char* buf, size_t n) { if (buf && n) snprintf(buf, n, "cpu_deconv_loops"); return 1; }
+extern "C" size_t mcn_deconv2d_workspace_bytes(mcn_conv_op op, const mcn_conv_geom* g, mcn_dtype dtype) {
+    DGeo d;
+    if (dgeo_from(g, dtype, &d) != MCN_OK || op == MCN_CONV_FWD) return 0;
+    return dc_swap_bytes(d) + (op == MCN_CONV_WGRAD ? mcn_bias_grad_workspace_bytes((int64_t)d.N * d.OH * d.OW, d.Cb) : 0);
+}
+extern "C" int mcn_filter_swap_io(const float* src, float* dst, int32_t taps, int32_t A, int32_t B, float scale, void*) {
+    if (!src || !dst || src == dst) return fail(MCN_E_BADARG, "filter_swap_io: null or aliased tensor");
+    if (taps <= 0 || A <= 0 || B <= 0) return fail(MCN_E_BADARG, "filter_swap_io: taps=%d A=%d B=%d", taps, A, B);
+    for (long t = 0; t < taps; ++t)
+        for (long a = 0; a < A; ++a)
+            for (long b = 0; b < B; ++b) dst[(t * B + b) * A + a] = src[(t * A + a) * B + b] * scale;
+    return MCN_OK;
+}
+extern "C" int mcn_deconv2d_fwd(const void* x, const float* w, const void*, const float* bias, void* y, const mcn_conv_geom* gg, mcn_dtype dtype, mcn_layout layout, void*,
+                                size_t, void*) {
+    DGeo d;
+    if (int rc = dgeo_from(gg, dtype, &d)) return rc;
+    if (layout != MCN_NHWC) return fail(MCN_E_UNSUPPORTED, "deconv: NHWC only");
+    if (!x || !w || !y) return fail(MCN_E_BADARG, "deconv fwd: null tensor");
+    return by_dtype(dtype, "deconv2d_fwd", [&](auto s) {
+        typedef decltype(s) S;
+        typedef typename S::T T;
+        const std::vector<float> wq = cast_weights<S>(w, (size_t)d.KH * d.KW * d.Cs * d.Cb);
+        const long rows = (long)d.N * d.OH;
+#pragma omp parallel for schedule(static)
+        for (long r_ = 0; r_ < rows; ++r_) {
+            const int n = (int)(r_ / d.OH), oy = (int)(r_ % d.OH);
+            std::vector<float> acc(d.Cb);
+            for (int ox = 0; ox < d.OW; ++ox) {
+                std::fill(acc.begin(), acc.end(), 0.f);
+                for (int r = 0; r < d.KH; ++r) {
+                    const int ty = oy + d.pT - r;
+                    if (ty < 0 || ty % d.SH || ty / d.SH >= d.h) continue;
+                    for (int q = 0; q < d.KW; ++q) {
+                        const int tx = ox + d.pL - q;
+                        if (tx < 0 || tx % d.SW || tx / d.SW >= d.w) continue;
+                        const T* xr = (const T*)x + (((long)n * d.h + ty / d.SH) * d.w + tx / d.SW) * d.Cs;
+                        const float* wr = wq.data() + (size_t)(r * d.KW + q) * d.Cs * d.Cb;
+                        for (int c = 0; c < d.Cs; ++c) {
+                            const float xv = S::ld(xr + c);
+                            for (int k = 0; k < d.Cb; ++k) acc[k] += xv * wr[(size_t)c * d.Cb + k];
+                        }
+                    }
+                }
+                T* yo = (T*)y + (((long)n * d.OH + oy) * d.OW + ox) * d.Cb;
+                for (int k = 0; k < d.Cb; ++k) S::st(yo + k, acc[k] + (bias ? bias[k] : 0.f));
+            }
+        }
+        return (int)MCN_OK;
+    });
+}
+extern "C" int mcn_deconv2d_dgrad(const void* dy, const float* w, const float* w_swapped, const void* w_swapped_packed, void* dx, const mcn_conv_geom* g, mcn_dtype dtype,
+                                  mcn_layout layout, void* workspace, size_t workspace_bytes, void* stream) {
+    DGeo d;
+    if (int rc = dgeo_from(g, dtype, &d)) return rc;
+    if (!dy || !dx || (!w && !w_swapped)) return fail(MCN_E_BADARG, "deconv dgrad: null tensor");
+    if (!w_swapped && w_swapped_packed) return fail(MCN_E_BADARG, "deconv dgrad: a packed operand without the swapped filter it was packed from");
+    if (!w_swapped) {
+        if (!workspace || workspace_bytes < dc_swap_bytes(d)) return fail(MCN_E_WORKSPACE, "deconv dgrad: workspace too small");
+        if (int rc = mcn_filter_swap_io(w, (float*)workspace, d.KH * d.KW, d.Cs, d.Cb, 1.f, stream)) return rc;
+        w_swapped = (const float*)workspace;
+    }
+    return mcn_conv2d_fwd(dy, w_swapped, nullptr, nullptr, dx, g, dtype, layout, nullptr, 0, stream);
+}
+extern "C" int mcn_deconv2d_wgrad(const void* x, const void* dy, float* dw, float* dbias, const mcn_conv_geom* g, float grad_scale, mcn_dtype dtype, mcn_layout layout,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    DGeo d;
+    if (int rc = dgeo_from(g, dtype, &d)) return rc;
+    if (!x || !dy || !dw) return fail(MCN_E_BADARG, "deconv wgrad: null tensor");
+    const size_t sb = dc_swap_bytes(d);
+    if (!workspace || workspace_bytes < sb) return fail(MCN_E_WORKSPACE, "deconv wgrad: workspace too small");
+    if (int rc = mcn_conv2d_wgrad(dy, x, (float*)workspace, nullptr, g, 1.f, dtype, layout, nullptr, 0, stream)) return rc;
+    if (int rc = mcn_filter_swap_io((const float*)workspace, dw, d.KH * d.KW, d.Cb, d.Cs, grad_scale, stream)) return rc;
+    if (!dbias) return MCN_OK;
+    return mcn_bias_grad(dy, dbias, (int64_t)d.N * d.OH * d.OW, d.Cb, grad_scale, dtype, (char*)workspace + sb, workspace_bytes - sb, stream);
+}

@@ -99,6 +99,8 @@ class Lowering(object):
                         gm.tile = t
                         need = max(need, lib.mcn_conv2d_workspace_bytes(op, ctypes.byref(gm), self.dt))
                     gm.tile = keep
+            elif n.op == 'deconv':
+                need = max(need, *[lib.mcn_deconv2d_workspace_bytes(op, ctypes.byref(n.attrs['geom']), self.dt) for op in (_ffi.CONV_FWD, _ffi.CONV_DGRAD, _ffi.CONV_WGRAD)])
             elif n.op == 'dwconv':
                 need = max(need, lib.mcn_dwconv2d_workspace_bytes(ctypes.byref(n.attrs['geom']), self.dt))
             elif n.op == 'bn':
@@ -223,6 +225,7 @@ class Lowering(object):
             self.model._packed_store = shared
         self.packed_ptr = {k: shared.data_ptr() + o for k, o in offs.items()}
         self.plan_weight_standardization()             # (first in the prepack program: the pair rebuilds and the pack below read w_hat)
+        jobs += self.plan_deconv_filters()             # (likewise: the batched pack below reads the swapped copies)
         for n in self.g.nodes:
             if n.op != 'conv':
                 continue
@@ -271,6 +274,34 @@ class Lowering(object):
         assert nbytes <= self.ws_bytes
         self.ws_table = torch.frombuffer(table, dtype=torch.uint8).to(self.g.device)
         self.prepack.add(lib.mcn_ws_fwd_run, self.ws_table.data_ptr(), ndesc, WS_EPS, self.ws_ptr, self.ws_bytes)
+
+    def plan_deconv_filters(self):
+        """Derived operands of every transposed convolution, refreshed once per step at the head of the prepack program (the w_hat store of
+        weight standardisation is the precedent): the forward's packed operand (mcn_deconv2d_pack) and, where the input takes a gradient, the
+        filter with its channel axes swapped (mcn_filter_swap_io) — the HWIO filter of the strided convolution that IS the data gradient —
+        whose packed form is one more job of the batched conv pack (returned).  Buffers are shared by the train and eval lowerings (masters vs
+        EMA shadows), like the packed conv operands."""
+        jobs = []
+        for n in self.g.nodes:
+            if n.op != 'deconv':
+                continue
+            gm, w = n.attrs['geom'], n.attrs['w']
+            buf = n.attrs.setdefault('deconv_buf', {})
+            nb = int(lib.mcn_deconv2d_packed_bytes(ctypes.byref(gm), self.dt))
+            if nb and 'packed' not in buf:
+                buf['packed'] = torch.zeros(nb, dtype=torch.uint8, device=self.g.device)
+            if nb:
+                self.prepack.add(lib.mcn_deconv2d_pack, self.vptr(w), buf['packed'].data_ptr(), ctypes.byref(gm), self.dt)
+            if self.train and n.inputs[0].needs_grad:
+                if 'swapped' not in buf:
+                    buf['swapped'] = torch.zeros(w.data.numel(), dtype=torch.float32, device=self.g.device)
+                self.prepack.add(lib.mcn_filter_swap_io, self.vptr(w), buf['swapped'].data_ptr(), gm.KH * gm.KW, gm.Cout, gm.Cin, 1.0)
+                nd = int(lib.mcn_conv2d_packed_bytes(_ffi.CONV_FWD, ctypes.byref(gm), self.dt))
+                if nd:
+                    if 'swapped_packed' not in buf:
+                        buf['swapped_packed'] = torch.zeros(nd, dtype=torch.uint8, device=self.g.device)
+                    jobs.append(_ffi.PackJob(buf['swapped'].data_ptr(), buf['swapped_packed'].data_ptr(), gm, _ffi.CONV_FWD, 0))
+        return jobs
 
     def wflat(self, n):
         """fp32 HWIO filter of conv node n in its original geometry: the variable (master / EMA shadow), or its standardised form"""
@@ -541,6 +572,28 @@ class Lowering(object):
                                                              ctypes.byref(gm), acc, self.dt, _ffi.NHWC, self.ws_ptr, self.ws_bytes))
         if late:
             emit_wgrad()
+
+    # ---- transposed convolution (reference convnet.py:2408-2498) -----------------------------------------------------
+    def fwd_deconv(self, n):
+        """inference reads the EMA shadows (vptr); the packed operand was refreshed from the same source by this lowering's prepack program"""
+        x, y = n.inputs[0], n.outputs[0]
+        pk = n.attrs['deconv_buf'].get('packed')
+        self.fwd.add(lib.mcn_deconv2d_fwd, x.buf.data_ptr(), self.vptr(n.attrs['w']), pk.data_ptr() if pk is not None else 0, self.vptr(n.attrs.get('b')),
+                     y.buf.data_ptr(), ctypes.byref(n.attrs['geom']), self.dt, _ffi.NHWC, self.ws_ptr, self.ws_bytes)
+
+    def bwd_deconv(self, n):
+        """data gradient = the strided convolution of dy on the main stream; filter gradient on the wgrad stream behind its event, like a conv's"""
+        x, y = n.inputs[0], n.outputs[0]
+        w, b, gm, buf = n.attrs['w'], n.attrs.get('b'), n.attrs['geom'], n.attrs['deconv_buf']
+        if x.needs_grad:
+            sp = buf.get('swapped_packed')
+            self.contribute_via_scratch(x, lambda dst: self.bwd.add(lib.mcn_deconv2d_dgrad, y.grad.data_ptr(), w.data.data_ptr(), buf['swapped'].data_ptr(),
+                                                                    sp.data_ptr() if sp is not None else 0, dst, ctypes.byref(gm), self.dt, _ffi.NHWC, self.ws_ptr, self.ws_bytes))
+        if w.trainable:
+            add, ws, wb = (self.bwd.add_side, self.ws2.data_ptr(), self.ws2.numel() * 4) if self.overlap_wgrad else (self.bwd.add, self.ws_ptr, self.ws_bytes)
+            add(lib.mcn_deconv2d_wgrad, x.buf.data_ptr(), y.grad.data_ptr(), w.grad.data_ptr(), b.grad.data_ptr() if b is not None else 0, ctypes.byref(gm),
+                1.0 / self.loss_scale, self.dt, _ffi.NHWC, ws, wb)
+            self.bwd.mark(('grad_ready', tuple(v.name for v in (w, b) if v is not None)))
 
     # ---- depthwise conv / squeeze-excite (EfficientNet MBConv, models/efficientnet.py:126-197) ----------------------
     def fwd_dwconv(self, n):
