@@ -430,6 +430,39 @@ int mcn_gn_bwd(const void* dy, const void* x, const void* y, const float* gamma,
                void* dx, void* dskip, float* dgamma, float* dbeta, float grad_scale, int32_t N, int64_t HW, int32_t C, int32_t G,
                mcn_act act, mcn_dtype dtype, int32_t path, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- grouped batch normalisation ----------------------------------------------------------
+ * replaces ConvNet.grouped_batch_norm in training mode with updating statistics (reference convnet.py:2176-2376; reached by
+ * normalization(norm_type='grouped_batch', norm_param=P), convnet.py:1770-1774).  x, y: [M][C] NHWC in `dtype`, M = N*H*W; group g owns
+ * the P channels [g*P, (g+1)*P), G = C/P; mean_g and the BIASED var_g run over the M*P elements of the group in fp32 (tf.nn.moments over
+ * axes [0, 1, 2, 4], convnet.py:2331):
+ *   y = act(gamma[c] * (x - mean_g) / sqrt(var_g + eps) + beta[c] [+ skip]), rounded once (convnet.py:2325, 2373-2375).
+ * gamma / beta: fp32 [C]; NULL = 1 / 0 (scale=False / shift=False, convnet.py:2267, 2286).  `skip` (same shape as y, may be NULL) and `act`
+ * (MCN_ACT_NONE, MCN_ACT_RELU or MCN_ACT_SWISH; anything else, or swish with a residual: MCN_E_UNSUPPORTED) are fused as in
+ * mcn_bn_fwd_train, with its rounding points.  save_mean / save_invstd: fp32 [G], kept for the backward pass.  batch_mean / batch_var
+ * (fp32 [C], may be NULL): mean_g and var_g tiled over the group's channels (convnet.py:2335-2340) — var_g stays BIASED, there is no
+ * M/(M-1) correction as in tf.nn.fused_batch_norm.  running_mean / running_var (fp32 [C], may be NULL):
+ * r <- momentum*r + (1-momentum)*batch (convnet.py:2352-2368).
+ * P: a divisor or a multiple of the 16-byte chunk (4 fp32 / 8 two-byte elements; P == C is a multiple), else MCN_E_UNSUPPORTED, as is a C
+ * that is not a multiple of the chunk; C % P != 0 and NULL tensors: MCN_E_BADARG; a short workspace (mcn_gbn_workspace_bytes):
+ * MCN_E_WORKSPACE.  Deterministic (no atomics): a repeated call is bit-identical.
+ * Evaluation and frozen statistics (update_batch_norm=False / a block outside blocks_to_train, convnet.py:2341-2344, 2369-2372) are the
+ * per-channel expression of mcn_bn_fwd_infer / mcn_bn_bwd_frozen: there is no grouped entry point for them.
+ *
+ * mcn_gbn_bwd: gradient of the above (tf.gradients through convnet.py:2330-2333, 2373 [+ the activation's gradient + the add's fan-out]).
+ * dz = dy masked by [y > 0] when act == RELU (y != NULL: the stored forward output, required when the forward fused a residual; y == NULL:
+ * recomputed from x as in mcn_bn_bwd) or dy * swish'(z) with z recomputed from x, the statistics, gamma and beta (dskip must be NULL).
+ * With xhat = (x - mean_g)*invstd_g and t = dz*gamma[c]:
+ *   dx = invstd_g * (t - (1/(M P)) sum_g t - xhat * (1/(M P)) sum_g t*xhat)
+ *   dgamma[c] = grad_scale * sum_M dz*xhat,  dbeta[c] = grad_scale * sum_M dz   (either may be NULL: frozen blocks_to_train)
+ *   dskip (may be NULL) receives dz. */
+size_t mcn_gbn_workspace_bytes(int64_t M, int32_t C, int32_t P);
+int mcn_gbn_fwd_train(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* save_mean, float* save_invstd,
+                      float* batch_mean, float* batch_var, float* running_mean, float* running_var, float momentum, int64_t M, int32_t C,
+                      int32_t P, float eps, mcn_act act, mcn_dtype dtype, void* workspace, size_t workspace_bytes, void* stream);
+int mcn_gbn_bwd(const void* dy, const void* x, const void* y, const float* gamma, const float* beta, const float* save_mean,
+                const float* save_invstd, void* dx, void* dskip, float* dgamma, float* dbeta, float grad_scale, int64_t M, int32_t C,
+                int32_t P, mcn_act act, mcn_dtype dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- weight standardisation --------------------------------------------------------------
  * replaces the weight_standardization branch of ConvNet.weight_variable (reference convnet.py:1410-1419; conv_layer(ws=True) in
  * models/resnet_v1_5_wsgn.py and models/efficientnet_wsgn.py).  An fp32 HWIO filter is the row-major matrix w[K][C], K = KH*KW*Cin rows,

@@ -168,6 +168,9 @@ SIGNATURES = {
     'mcn_gn_resident_ok': (c_int32, [c_int32, c_int32, c_int64, c_int32, c_int32, c_int]),
     'mcn_gn_fwd': (c_int, [c_void_p] * 7 + [c_int32, c_int64, c_int32, c_int32, c_float, c_int, c_int, c_int32, c_void_p, c_size_t, c_void_p]),
     'mcn_gn_bwd': (c_int, [c_void_p] * 10 + [c_float, c_int32, c_int64, c_int32, c_int32, c_int, c_int, c_int32, c_void_p, c_size_t, c_void_p]),
+    'mcn_gbn_workspace_bytes': (c_size_t, [c_int64, c_int32, c_int32]),
+    'mcn_gbn_fwd_train': (c_int, [c_void_p] * 11 + [c_float, c_int64, c_int32, c_int32, c_float, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'mcn_gbn_bwd': (c_int, [c_void_p] * 11 + [c_float, c_int64, c_int32, c_int32, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     'mcn_global_avgmax_pool_workspace_bytes': (c_size_t, [c_int32, c_int64, c_int32]),
     'mcn_global_avgmax_pool_fwd': (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int, c_void_p, c_size_t, c_void_p]),
     'mcn_global_avgmax_pool_bwd': (c_int, [c_void_p] * 5 + [c_int32, c_int32, c_int64, c_int32, c_int, c_void_p]),

@@ -36,9 +36,9 @@ if os.environ.get('MCN_EXTRA_CFLAGS'):                   # experiment builds (e.
     import hashlib as _h
     FLAGS += os.environ['MCN_EXTRA_CFLAGS'].split()
     OBJ = os.path.join(CSRC, '_obj_x' + _h.sha1(os.environ['MCN_EXTRA_CFLAGS'].encode()).hexdigest()[:8])
-# per-source flags.  cbam.hip, gn.hip, ws.hip: scalar fp32 math only (no v_pk_*_f32 forms; their kernels are HBM-bound, the packed forms buy nothing there)
+# per-source flags.  cbam.hip, gbn.hip, gn.hip, ws.hip: scalar fp32 math only (no v_pk_*_f32 forms; their kernels are HBM-bound, the packed forms buy nothing there)
 _NO_PK = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
-SOURCE_FLAGS = {'cbam.hip': _NO_PK, 'gn.hip': _NO_PK, 'ws.hip': _NO_PK}
+SOURCE_FLAGS = {'cbam.hip': _NO_PK, 'gbn.hip': _NO_PK, 'gn.hip': _NO_PK, 'ws.hip': _NO_PK}
 PROBES = os.environ.get('MCN_KERNEL_PROBES') == '1'
 if PROBES:
     FLAGS.append('-DMCN_KERNEL_PROBES=1')

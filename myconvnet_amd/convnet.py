@@ -10,9 +10,12 @@ What differs by design: there is no TF session — `_build_model` records a stat
 Weight standardisation (conv_layer(ws=True), reference convnet.py:1410-1419) is built for ordinary convolutions: the
 executor standardises every such filter in one batched launch pair per step and the conv reads w_hat in place of the master.
 
+Grouped batch normalisation (grouped_batch_norm, reference convnet.py:2176-2376; norm_type='grouped_batch') is built for NHWC: one 'gbn'
+node on csrc/gbn.hip in training, the batch-norm inference / frozen kernels otherwise.
+
 Not built (raise NotImplementedError): weight standardisation of depthwise filters and of fc_layer, the normalization()
-dispatcher for anything but 'batch' (group_norm itself is built: a model calls it from _build_model),
-augmentation, dropout rate > 0 (SURVEY.md §8f "next" rows).
+dispatcher for norm_type='group' (group_norm itself is built: a model calls it from _build_model), grouped_batch_norm with
+channel_first, augmentation, dropout rate > 0 (SURVEY.md §8f "next" rows).
 
 Transposed convolution (transposed_conv_layer, reference convnet.py:2408-2498) is built for dilation 1, NHWC, without weight standardisation:
 one 'deconv' node, forward in csrc/deconv.hip, backward on the strided convolution's kernels.
@@ -416,6 +419,13 @@ class ConvNet(object):
                 mu, sg = a['mu'], a['sigma']
                 a['saved'] = dict(mean=torch.zeros(c, dtype=torch.float32, device=dev), invstd=torch.zeros(c, dtype=torch.float32, device=dev),
                                   bmean=self.batch_stats[mu.offset:mu.offset + c], bvar=self.batch_stats[sg.offset:sg.offset + c])
+            elif n.op == 'gbn':
+                a = n.attrs
+                c = n.inputs[0].shape[-1]
+                mu, sg = a['mu'], a['sigma']
+                ng = c // a['cpg']                          # saved statistics per group; batch statistics tiled per channel, as batch norm's
+                a['saved'] = dict(mean=torch.zeros(ng, dtype=torch.float32, device=dev), invstd=torch.zeros(ng, dtype=torch.float32, device=dev),
+                                  bmean=self.batch_stats[mu.offset:mu.offset + c], bvar=self.batch_stats[sg.offset:sg.offset + c])
             elif n.op == 'gn':
                 ng = n.inputs[0].shape[0] * n.attrs['groups']
                 n.attrs['saved'] = dict(mean=torch.zeros(ng, dtype=torch.float32, device=dev), invstd=torch.zeros(ng, dtype=torch.float32, device=dev))
@@ -722,14 +732,18 @@ class ConvNet(object):
 
     def normalization(self, x, norm_type='batch', norm_param=None, scale=True, shift=True, zero_scale_init=False, epsilon=1e-3,
                       scope='norm'):
-        """reference convnet.py:1757-1778.  Only 'batch' is dispatched: norm_type='group' still raises although group_norm() is built
-        (tests/test_host_logic.py pins the NotImplementedError; routing it to self.group_norm(x, num_groups=norm_param, ...) as
-        convnet.py:1765-1769 does is the follow-up) — a model reaches group norm by calling self.group_norm directly."""
+        """reference convnet.py:1757-1778.  'batch' and 'grouped_batch' (norm_param = channels per group, None -> 8: convnet.py:1770-1774)
+        are dispatched: norm_type='group' still raises although group_norm() is built (tests/test_host_logic.py pins the
+        NotImplementedError; routing it to self.group_norm(x, num_groups=norm_param, ...) as convnet.py:1765-1769 does is the follow-up)
+        — a model reaches group norm by calling self.group_norm directly."""
         if norm_type is None:
             return x
         if norm_type.lower() == 'batch':
             return self.batch_norm(x, scale=scale, shift=shift, zero_scale_init=zero_scale_init, epsilon=epsilon, scope=scope)
-        raise NotImplementedError('normalization type {} is outside the built path (supported: batch)'.format(norm_type))
+        if norm_type.lower() == 'grouped_batch':
+            return self.grouped_batch_norm(x, num_channels_per_group=8 if norm_param is None else norm_param, scale=scale, shift=shift,
+                                           zero_scale_init=zero_scale_init, epsilon=epsilon, scope=scope)
+        raise NotImplementedError('normalization type {} is outside the built path (supported: batch, grouped_batch)'.format(norm_type))
 
     def batch_norm(self, x, scale=True, shift=True, zero_scale_init=False, epsilon=1e-3, scope='bn'):
         """reference convnet.py:1780-1926 -> tf.nn.fused_batch_norm + running-statistics update."""
@@ -789,6 +803,48 @@ class ConvNet(object):
             name = self.scope_name()
         y = self.graph.tensor(x.shape, x.dtype, name, self._channel_first)
         self.graph.node('gn', [x], [y], scope=name, gamma=gamma, beta=beta, groups=int(num_groups), eps=epsilon, has_params=True)
+        return y
+
+    def grouped_batch_norm(self, x, num_channels_per_group=8, scale=True, shift=True, zero_scale_init=False, epsilon=1e-3, scope='gbn'):
+        """reference convnet.py:2176-2376: batch statistics over groups of num_channels_per_group adjacent channels (mean and BIASED
+        variance over N x H x W x channels-per-group in fp32), per-channel gamma / beta and running mu / sigma that hold the group's
+        statistics tiled over its channels; 4-D and 2-D ([B, C]) inputs.  One 'gbn' graph node (mcn_gbn_fwd_train / mcn_gbn_bwd) with its
+        saved [G] statistics; relu, swish and add(skip) [-> relu] fuse into it as into batch norm.  Evaluation and frozen statistics are
+        per-channel expressions of the moving statistics: the batch-norm kernels (mcn_bn_fwd_infer / mcn_bn_bwd_frozen).  The
+        `initialize` ops (convnet.py:2289-2314) average statistics restored from a batch-norm checkpoint; on fresh variables they are
+        the identity, and checkpoint restore is not built."""
+        if self._channel_first:
+            raise NotImplementedError('grouped_batch_norm: channel_first is not built')
+        if isinstance(self._update_batch_norm, bool):
+            update = self._update_batch_norm
+        else:
+            update = self._trainable_here()
+        trainable = self._trainable_here()
+        c = x.shape[-1]
+        p = int(num_channels_per_group)
+        with self.variable_scope(scope):
+            assert c // p * p == c, 'Number of channels must be a multiple of num_channels_per_group ({})'.format(num_channels_per_group)
+            mu = self._new_variable('mu', c, 'mu', zeros(), False)
+            sigma = self._new_variable('sigma', c, 'sigma', ones(), False)       # running VARIANCE despite the name
+            for v in (mu, sigma):
+                self.add_to_collection('norm_statistics', v)
+                self.add_to_collection('block_{}/norm_statistics'.format(self._curr_block), v)
+            gamma = beta = None
+            if scale:
+                gamma = self._new_variable('gamma', c, 'gamma', zeros() if zero_scale_init else ones(), trainable)
+                self._params += c
+            if shift:
+                beta = self._new_variable('beta', c, 'beta', zeros(), trainable)
+                self._params += c
+                self._flops += x.shape[1] * x.shape[2] * c if len(x.shape) == 4 else c
+            for v in (gamma, beta):
+                if v is not None:
+                    self.add_to_collection('norm_variables', v)
+                    self.add_to_collection('block_{}/norm_variables'.format(self._curr_block), v)
+            name = self.scope_name()
+        y = self.graph.tensor(x.shape, x.dtype, name, self._channel_first)
+        self.graph.node('gbn', [x], [y], scope=name, gamma=gamma, beta=beta, mu=mu, sigma=sigma, cpg=p, eps=epsilon,
+                        momentum=self._batch_norm_decay, update=update, has_params=True)
         return y
 
     def _pool(self, op, x, side_l, stride, padding):

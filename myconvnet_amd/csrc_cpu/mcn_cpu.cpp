@@ -806,6 +806,118 @@ extern "C" int mcn_gn_bwd(const void* dy, const void* x, const void* y, const fl
     });
 }
 
+// ---- grouped batch normalisation (convnet.py:2176-2376) ----------------------------------------------------------------------------------
+extern "C" size_t mcn_gbn_workspace_bytes(int64_t M, int32_t C, int32_t P) { return (M > 0 && C > 0 && P > 0) ? 256 : 0; }
+static int gbn_check(const char* who, int64_t M, int32_t C, int32_t P, mcn_act act, bool residual, mcn_dtype dtype, const void* ws, size_t ws_bytes) {
+    if (M <= 0 || C <= 0 || P <= 0) return fail(MCN_E_BADARG, "%s: bad argument", who);
+    if (C % P) return fail(MCN_E_BADARG, "%s: %d channels are not a multiple of %d channels per group", who, C, P);
+    if (dtype != MCN_F32 && dtype != MCN_BF16 && dtype != MCN_F16) return fail(MCN_E_UNSUPPORTED, "%s: dtype %d unsupported", who, (int)dtype);
+    const int vec = dtype == MCN_F32 ? 4 : 8;
+    if (C % vec) return fail(MCN_E_UNSUPPORTED, "%s: C = %d is not a multiple of the 16-byte chunk", who, C);
+    if (P % vec && vec % P) return fail(MCN_E_UNSUPPORTED, "%s: %d channels per group neither divide nor are a multiple of the 16-byte chunk", who, P);
+    if (act != MCN_ACT_NONE && act != MCN_ACT_RELU && act != MCN_ACT_SWISH) return fail(MCN_E_UNSUPPORTED, "%s: activation %d is not fused (none / relu / swish)", who, (int)act);
+    if (act == MCN_ACT_SWISH && residual) return fail(MCN_E_UNSUPPORTED, "%s: swish with a fused residual is not built", who);
+    if (!ws || ws_bytes < mcn_gbn_workspace_bytes(M, C, P)) return fail(MCN_E_WORKSPACE, "%s: workspace too small", who);
+    return MCN_OK;
+}
+extern "C" int mcn_gbn_fwd_train(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* save_mean, float* save_invstd, float* batch_mean,
+                                 float* batch_var, float* running_mean, float* running_var, float momentum, int64_t M, int32_t C, int32_t P, float eps, mcn_act act,
+                                 mcn_dtype dtype, void* ws, size_t ws_bytes, void*) {
+    if (!x || !y || !save_mean || !save_invstd) return fail(MCN_E_BADARG, "gbn_fwd_train: null tensor");
+    const int rc = gbn_check("gbn_fwd_train", M, C, P, act, skip != nullptr, dtype, ws, ws_bytes);
+    if (rc != MCN_OK) return rc;
+    return by_dtype(dtype, "gbn_fwd_train", [&](auto s) {
+        typedef decltype(s) S;
+        typedef typename S::T T;
+        const T* xp = (const T*)x;
+        const T* sp = (const T*)skip;
+        T* yp = (T*)y;
+        std::vector<float> sc(C), sh(C);
+#pragma omp parallel for schedule(static)
+        for (int g = 0; g < C / P; ++g) {
+            const int c0 = g * P;
+            const double piv = S::ld(xp + c0);
+            double a = 0.0, b = 0.0;
+            for (int64_t m = 0; m < M; ++m)
+                for (int c = c0; c < c0 + P; ++c) {
+                    const double d = (double)S::ld(xp + m * C + c) - piv;
+                    a += d;
+                    b += d * d;
+                }
+            const double cnt = (double)M * P, dm = a / cnt;
+            double var = b / cnt - dm * dm;                            // biased: no M/(M-1) (convnet.py:2337-2340)
+            if (var < 0.0) var = 0.0;
+            const float fmean = (float)(piv + dm), finv = (float)(1.0 / std::sqrt(var + (double)eps)), fvar = (float)var;
+            save_mean[g] = fmean;
+            save_invstd[g] = finv;
+            for (int c = c0; c < c0 + P; ++c) {
+                if (batch_mean) batch_mean[c] = fmean;
+                if (batch_var) batch_var[c] = fvar;
+                if (running_mean) running_mean[c] = momentum * running_mean[c] + (1.f - momentum) * fmean;
+                if (running_var) running_var[c] = momentum * running_var[c] + (1.f - momentum) * fvar;
+                sc[c] = (gamma ? gamma[c] : 1.f) * finv;
+                sh[c] = (beta ? beta[c] : 0.f) - fmean * sc[c];
+            }
+        }
+#pragma omp parallel for schedule(static)
+        for (int64_t m = 0; m < M; ++m)
+            for (int c = 0; c < C; ++c) {
+                float o = fmaf(S::ld(xp + m * C + c), sc[c], sh[c]);
+                if (sp) o += S::ld(sp + m * C + c);
+                if (act == MCN_ACT_RELU) o = o > 0.f ? o : 0.f;
+                if (act == MCN_ACT_SWISH) o = o * sigmoidf(o);
+                S::st(yp + m * C + c, o);
+            }
+        return (int)MCN_OK;
+    });
+}
+extern "C" int mcn_gbn_bwd(const void* dy, const void* x, const void* y, const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, void* dx,
+                           void* dskip, float* dgamma, float* dbeta, float grad_scale, int64_t M, int32_t C, int32_t P, mcn_act act, mcn_dtype dtype, void* ws,
+                           size_t ws_bytes, void*) {
+    if (!dy || !x || !dx || !save_mean || !save_invstd) return fail(MCN_E_BADARG, "gbn_bwd: null tensor");
+    const int rc = gbn_check("gbn_bwd", M, C, P, act, dskip != nullptr, dtype, ws, ws_bytes);
+    if (rc != MCN_OK) return rc;
+    return by_dtype(dtype, "gbn_bwd", [&](auto s) {
+        typedef decltype(s) S;
+        typedef typename S::T T;
+        const T* dyp = (const T*)dy;
+        const T* xp = (const T*)x;
+        const T* yp = (const T*)y;
+        T* dxp = (T*)dx;
+        T* dsp = (T*)dskip;
+#pragma omp parallel for schedule(static)
+        for (int g = 0; g < C / P; ++g) {
+            const int c0 = g * P;
+            const float mu = save_mean[g], is = save_invstd[g];
+            auto dz = [&](int64_t m, int c) {
+                const float sc = (gamma ? gamma[c] : 1.f) * is, sh = (beta ? beta[c] : 0.f) - mu * sc;
+                return act_grad<S>(act, dyp, xp, yp, nullptr, m, C, c, sc, sh);
+            };
+            double A = 0.0, B = 0.0;
+            for (int c = c0; c < c0 + P; ++c) {
+                double a = 0.0, b = 0.0;
+                for (int64_t m = 0; m < M; ++m) {
+                    const float gz = dz(m, c);
+                    a += gz;
+                    b += (double)gz * ((S::ld(xp + m * C + c) - mu) * is);
+                }
+                if (dbeta) dbeta[c] = (float)a * grad_scale;
+                if (dgamma) dgamma[c] = (float)b * grad_scale;
+                A += (gamma ? gamma[c] : 1.f) * a;
+                B += (gamma ? gamma[c] : 1.f) * b;
+            }
+            const float ca = (float)(A / ((double)M * P)), cb = (float)(B / ((double)M * P));
+            for (int c = c0; c < c0 + P; ++c)
+                for (int64_t m = 0; m < M; ++m) {
+                    const float gz = dz(m, c), xh = (S::ld(xp + m * C + c) - mu) * is;
+                    S::st(dxp + m * C + c, is * ((gamma ? gamma[c] : 1.f) * gz - ca - xh * cb));
+                    if (dsp) S::st(dsp + m * C + c, gz);
+                }
+        }
+        return (int)MCN_OK;
+    });
+}
+
 // ---- CBAM attention tail (models/resnet_v2_d_cbam.py:159-211; mcn.h) -------------------------------------------------------------------------
 extern "C" size_t mcn_global_avgmax_pool_workspace_bytes(int32_t N, int64_t HW, int32_t C) { return (N > 0 && HW > 0 && C > 0) ? 256 : 0; }
 // [dt | per-pixel ties | ds (2 per pixel)]

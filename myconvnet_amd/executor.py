@@ -108,6 +108,9 @@ class Lowering(object):
                 need = max(need, lib.mcn_bn_workspace_bytes(x.numel // x.shape[-1], x.shape[-1]))
             elif n.op == 'gn':
                 need = max(need, lib.mcn_gn_workspace_bytes(*self._gn_dims(n)))
+            elif n.op == 'gbn':
+                M, C, P = self._gbn_dims(n)                # (frozen statistics run mcn_bn_bwd_frozen)
+                need = max(need, lib.mcn_gbn_workspace_bytes(M, C, P), lib.mcn_bn_workspace_bytes(M, C))
             elif n.op == 'fc':
                 x = n.inputs[0]
                 need = max(need, lib.mcn_fc_workspace_bytes(x.shape[0], x.shape[1], n.outputs[0].shape[1], self.dt))
@@ -1038,6 +1041,73 @@ class Lowering(object):
             self.contribute_via_scratch(x, emit)
         else:
             emit(self.scratch_like(x, 'gn_dx').data_ptr())
+        if post:
+            self.bwd.add(lib.mcn_accumulate, *post)
+        self.bwd.mark(('grad_ready', tuple(v.name for v in (g, b) if v is not None and v.trainable)))
+
+    # ---- grouped batch norm (convnet.py:2176-2376) ----------------------------------------------------------------------------
+    def _gbn_dims(self, n):
+        """(M, C, P) of a grouped batch norm node: 4-D NHWC or the reference's 2-D [B, C] case"""
+        x = n.inputs[0]
+        assert x.cs == x.shape[-1], 'grouped batch norm needs a dense channel axis'
+        return x.numel // x.shape[-1], x.shape[-1], n.attrs['cpg']
+
+    def fwd_gbn(self, n):
+        """Training with updating statistics: mcn_gbn_fwd_train (it updates mu / sigma itself with one rank; the cross-rank chain of
+        optimizers.py reads the tiled per-channel batch statistics otherwise).  Evaluation and frozen statistics are the per-channel
+        expression of the moving statistics (convnet.py:2341-2344, 2369-2372): mcn_bn_fwd_infer.  None of fwd_bn's shortcuts (conv-epilogue
+        statistics, byte masks, pool / gap fusions) applies: they key on op == 'bn'."""
+        x, y = n.inputs[0], n.outputs[0]
+        a = n.attrs
+        M, C, P = self._gbn_dims(n)
+        skip = a.get('skip')
+        if self.train and a['update']:
+            st = a['saved']
+            single = self.model.world_size == 1
+            self.fwd.add(lib.mcn_gbn_fwd_train, x.buf.data_ptr(), self.vptr(a['gamma']), self.vptr(a['beta']), ptr(skip.buf) if skip else 0, y.buf.data_ptr(),
+                         st['mean'].data_ptr(), st['invstd'].data_ptr(), st['bmean'].data_ptr(), st['bvar'].data_ptr(),
+                         a['mu'].data.data_ptr() if single else 0, a['sigma'].data.data_ptr() if single else 0, float(a['momentum']), M, C, P,
+                         float(a['eps']), a.get('act', 0), MCN_DT[x.dtype], self.ws_ptr, self.ws_bytes)
+        else:
+            mu, sg = a['mu'], a['sigma']
+            self.fwd.add(lib.mcn_bn_fwd_infer, x.buf.data_ptr(), self.vptr(a['gamma']), self.vptr(a['beta']), mu.data.data_ptr() if self.train else mu.ema.data_ptr(),
+                         sg.data.data_ptr() if self.train else sg.ema.data_ptr(), ptr(skip.buf) if skip else 0, y.buf.data_ptr(), M, C, float(a['eps']),
+                         a.get('act', 0), MCN_DT[x.dtype])
+
+    def bwd_gbn(self, n):
+        """The skip gradient takes the generic contribute / scratch route, as group norm's.  ReLU without a fused residual: the mask is
+        recomputed from x inside the kernel (y pointer = 0), as in bwd_bn."""
+        x, y = n.inputs[0], n.outputs[0]
+        a = n.attrs
+        M, C, P = self._gbn_dims(n)
+        skip = a.get('skip')
+        st = a['saved']
+        g, b = a['gamma'], a['beta']
+        act = a.get('act', 0)
+        dskip_ptr, post = 0, None
+        if skip is not None and skip.needs_grad:
+            if skip.id not in self.written:
+                self.written.add(skip.id)
+                dskip_ptr = skip.grad.data_ptr()
+            else:
+                s = self.scratch_like(skip, 'gbn_dskip')
+                dskip_ptr = s.data_ptr()
+                post = (skip.grad.data_ptr(), s.data_ptr(), skip.grad.numel(), MCN_DT[skip.dtype])
+        grads = [g.grad.data_ptr() if g is not None and g.trainable else 0, b.grad.data_ptr() if b is not None and b.trainable else 0, 1.0 / self.loss_scale]
+
+        def emit(dst):
+            if not a['update']:                              # statistics are constants: the affine gradient of batch norm
+                self.bwd.add(lib.mcn_bn_bwd_frozen, y.grad.data_ptr(), x.buf.data_ptr(), y.buf.data_ptr(), self.vptr(g), self.vptr(b), a['mu'].data.data_ptr(),
+                             a['sigma'].data.data_ptr(), float(a['eps']), dst, dskip_ptr, *(grads + [M, C, act, MCN_DT[x.dtype], self.ws_ptr, self.ws_bytes]))
+                return
+            yptr = y.buf.data_ptr() if skip is not None else 0
+            self.bwd.add(lib.mcn_gbn_bwd, y.grad.data_ptr(), x.buf.data_ptr(), yptr, self.vptr(g), self.vptr(b), st['mean'].data_ptr(), st['invstd'].data_ptr(),
+                         dst, dskip_ptr, *(grads + [M, C, P, act, MCN_DT[x.dtype], self.ws_ptr, self.ws_bytes]))
+        # (a frozen block's gbn still runs when its skip branch needs dz: dx then goes to scratch)
+        if x.needs_grad:
+            self.contribute_via_scratch(x, emit)
+        else:
+            emit(self.scratch_like(x, 'gbn_dx').data_ptr())
         if post:
             self.bwd.add(lib.mcn_accumulate, *post)
         self.bwd.mark(('grad_ready', tuple(v.name for v in (g, b) if v is not None and v.trainable)))

@@ -239,7 +239,8 @@ class Graph(object):
     def fuse(self):
         """bn -> relu, bn -> swish, bn -> add(skip) [-> relu]: the activation and the residual add run inside the
         BN apply pass (one read + one write instead of three / five).  A group norm ('gn') absorbs relu and add(skip) [-> relu]
-        the same way (the tail of the reference's *_wsgn residual unit); swish behind it stays a node of its own."""
+        the same way (the tail of the reference's *_wsgn residual unit); swish behind it stays a node of its own.  A grouped batch
+        norm ('gbn') absorbs all three exactly as 'bn' does."""
         alive = list(self.nodes)
 
         def sole_consumer(t, op):
@@ -249,7 +250,7 @@ class Graph(object):
         while changed:
             changed = False
             for n in alive:
-                if n.op not in ('bn', 'gn') or n.attrs.get('act', 0) or not n.attrs.get('training_graph', True):
+                if n.op not in ('bn', 'gn', 'gbn') or n.attrs.get('act', 0) or not n.attrs.get('training_graph', True):
                     continue
                 y = n.outputs[0]
                 if n.attrs.get('skip') is None and sole_consumer(y, 'add') and y.consumers[0].inputs[0] is y \
@@ -268,7 +269,7 @@ class Graph(object):
                         alive.remove(add)
                         changed = True
                         break
-                if n.op == 'bn' and n.attrs.get('skip') is None and sole_consumer(y, 'act') and y.consumers[0].attrs['kind'] == _ffi.ACT_SWISH:
+                if n.op in ('bn', 'gbn') and n.attrs.get('skip') is None and sole_consumer(y, 'act') and y.consumers[0].attrs['kind'] == _ffi.ACT_SWISH:
                     sw = y.consumers[0]                     # bn -> swish (every EfficientNet conv): one apply pass
                     n.attrs['act'] = _ffi.ACT_SWISH
                     y.alias_of = sw.outputs[0]

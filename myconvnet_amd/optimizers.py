@@ -172,7 +172,7 @@ class Optimizer(object):
                 # pass READS the running statistics while this chain runs on its own stream): maximal runs of updating ranges
                 runs = []
                 for n_ in m.graph.nodes:
-                    if n_.op == 'bn' and n_.attrs['update']:
+                    if n_.op in ('bn', 'gbn') and n_.attrs['update']:      # (gbn: the group's statistics tiled over its channels, the same [C] slots)
                         for v in (n_.attrs['mu'], n_.attrs['sigma']):
                             s0, e0 = v.offset, v.offset + (v.size + 3) // 4 * 4
                             runs.append([s0, e0])
